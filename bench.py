@@ -6,7 +6,18 @@ configs[1], "C2").  N GPUs run N independent replicas (inference does not
 shard further; no collective on the data path) -> weak scaling; value =
 images/sec over all ranks, timed as max over ranks between barriers.
 
-Extra fields on the one JSON line:
+A plain run sets up, warms up, times --steps forwards, writes the outputs of
+the last timed forward if --dump-outputs DIR is given, and prints the one JSON
+line (metric, value, unit, ms_per_step, ...).  Everything else is measured
+only with --full.
+
+--dump-outputs DIR: loc / conf / landm of the last timed forward as float32
+DIR/<name>.npy (rank 0).  Model weights and inputs are seeded, so two builds
+run with the same arguments can be compared output for output.  Above
+DUMP_BYTES the same seeded sample of (image, anchor) rows is written for all
+three.
+
+Extra fields on the one JSON line with --full:
   roofline     conv-GEMM stack (the dominant kernel family) vs the fp32 MFMA
                peak: algorithmic FLOPs of every jabd conv launch in one step /
                their summed HIP-event durations on the launch stream.
@@ -57,6 +68,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--size", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (roofline, variants, "
+                         "training, NMS, predict, CPU baseline); the --no-* switches trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed forward's outputs to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-nms", action="store_true")
     ap.add_argument("--no-predict", action="store_true")
@@ -67,6 +83,29 @@ def parse():
     ap.add_argument("--pmc-forward-only", action="store_true",
                     help="run exactly --steps eval forwards and nothing else (PMC passes)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs writes at most this many bytes of float32
+
+
+def dump_outputs(out, directory):
+    """--dump-outputs: (loc, conf, landm) [B, A, 4 | 2 | 10] of one forward as
+    float32 DIR/<name>.npy.  Outputs larger than DUMP_BYTES in all are written
+    as [n, k]: the same n (image, anchor) rows of each, drawn once with a
+    fixed seed and kept in order."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    rows = out[0].shape[0] * out[0].shape[1]
+    row_bytes = 4 * sum(o.shape[2] for o in out)
+    keep = None
+    if rows * row_bytes > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_BYTES // row_bytes,
+                                                       replace=False))
+    for name, o in zip(("loc", "conf", "landm"), out):
+        a = o.detach().float().cpu().numpy()
+        if keep is not None:
+            a = a.reshape(rows, -1)[keep]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
 
 
 def build_model(device):
@@ -975,9 +1014,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     with torch.no_grad():
         for _ in range(args.steps):
-            model(x)
+            out = model(x)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -989,7 +1029,31 @@ def main():
     n_gpus = world
     imgs = args.batch * args.steps * n_gpus
     value = imgs / el
+    if rank == 0 and args.dump_outputs and out is not None:
+        dump_outputs(out, args.dump_outputs)
+    del out
 
+    extra = full_legs(args, model, x, device, dist, rank, world) if args.full else {}
+    if rank == 0:
+        line = {
+            "metric": METRIC, "value": value, "unit": "images/sec", "n_gpus": n_gpus,
+            "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "fp32", "data": "synthetic",
+            "config": {"workload": "C2: JABD-MobileNetV3 RetinaFace (nets/retinaface_r.py) "
+                       "eval forward, weights_init weights", "global_batch": args.batch * n_gpus,
+                       "image_size": args.size, "parallelism": f"replicas x{n_gpus}"},
+        }
+        line.update(extra)
+        print(json.dumps(line), flush=True)
+    if dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_legs(args, model, x, device, dist, rank, world):
+    """--full: every leg besides the headline C2 loop (module docstring), run
+    after it; returns the extra fields of the JSON line (rank 0's are kept)."""
     extra = {}
     if rank == 0:
         # conv-stack roofline on the C2 model right after its timed loop (before
@@ -1051,20 +1115,7 @@ def main():
             extra["c5_e2e"] = c5_e2e(device)
         if world == 1 and not args.no_cpu_baseline:
             extra["cpu_baseline"] = cpu_baseline(args.size, args.cpu_seconds)
-        line = {
-            "metric": METRIC, "value": value, "unit": "images/sec", "n_gpus": n_gpus,
-            "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "fp32", "data": "synthetic",
-            "config": {"workload": "C2: JABD-MobileNetV3 RetinaFace (nets/retinaface_r.py) "
-                       "eval forward, weights_init weights", "global_batch": args.batch * n_gpus,
-                       "image_size": args.size, "parallelism": f"replicas x{n_gpus}"},
-        }
-        line.update(extra)
-        print(json.dumps(line), flush=True)
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    return extra
 
 
 if __name__ == "__main__":

@@ -2,7 +2,8 @@
 
 bench.py is launched exactly as the driver launches it for N GPUs
 (`python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1
-... bench.py --gpus 2`), with the process-group backend taken from the
+... bench.py --full --gpus 2`; the training leg is behind --full), with the
+process-group backend taken from the
 environment (JABD_DIST_BACKEND=gloo: the same control flow as RCCL, on the
 one GPU both ranks share) and JABD_BENCH_GLOBAL_DATA=1 (the ranks shard one
 global synthetic batch, so the job is comparable with one process).
@@ -35,7 +36,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZE, B = 96, 2
-WARMUP, TIMER_STEPS, STEPS = 3, 1, 2     # bench.main: C4 warmup 3, one conv-timer step
+WARMUP, TIMER_STEPS, STEPS = 3, 1, 2     # bench.full_legs: C4 warmup 3, one conv-timer step
 
 
 def _free_port():
@@ -49,7 +50,7 @@ def _free_port():
 def _run_bench(world, tmp_path):
     env = dict(os.environ, JABD_DIST_BACKEND="gloo", JABD_BENCH_GLOBAL_DATA="1",
                MASTER_ADDR="127.0.0.1")
-    args = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1",
+    args = ["bench.py", "--full", "--gpus", str(world), "--steps", "2", "--warmup", "1",
             "--size", str(SIZE), "--batch", str(B), "--train-steps", str(STEPS),
             "--r50-batch", "0", "--no-nms", "--no-predict", "--no-cpu-baseline"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",

@@ -16,7 +16,7 @@ timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $T/pmc_fet
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $T/pmc_write -o run -- python3 bench.py --steps 3 --pmc-forward-only > $O/pmc_write.log 2>&1 &&
 python3 tools/pmc_traffic.py $T/pmc_fetch $T/pmc_write 3 $O/pmc_traffic.json &&
 cp $O/pmc_traffic.json profiles/$R/pmc_traffic.json &&
-timeout -k 10 500 python -u bench.py > $O/bench.log 2>&1 && tail -1 $O/bench.log > $O/bench_line.json &&
+timeout -k 10 500 python -u bench.py --full > $O/bench.log 2>&1 && tail -1 $O/bench.log > $O/bench_line.json &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $T/prof_fwd -o run -- python3 bench.py --steps 10 --pmc-forward-only > $O/prof_fwd.log 2>&1 &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $T/prof_tr_mnv3 -o run -- python3 tools/train_steps.py --kind mnv3 > $O/tr_mnv3.log 2>&1 &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $T/prof_tr_r50 -o run -- python3 tools/train_steps.py --kind r50 --batch 64 --steps 2 > $O/tr_r50.log 2>&1 &&

@@ -6,7 +6,7 @@ O=gpurun_out/knobs
 mkdir -p $O
 run() {  # name env...
   local n=$1; shift
-  env "$@" timeout -k 10 200 python3 -u bench.py --no-train --no-nms --no-predict --no-cpu-baseline --r50-batch 0 > $O/$n.log 2>&1 || return 1
+  env "$@" timeout -k 10 200 python3 -u bench.py --full --no-train --no-nms --no-predict --no-cpu-baseline --r50-batch 0 > $O/$n.log 2>&1 || return 1
   python3 -c "import json,sys; d=json.loads(open('$O/$n.log').read().strip().splitlines()[-1]); print('$n', round(d['value'],1), round(d['roofline']['frac'],4), round(d['roofline']['conv_ms_per_step'],3))" >> $O/summary.txt
 }
 for r in 1 2; do
