@@ -40,6 +40,19 @@ int64_t jabd_abi_struct_size(int32_t which);
 /* Copies the calling thread's last error message into buf (NUL-terminated). */
 int jabd_last_error(char* buf, size_t len);
 
+/* Launch witness (tests, diagnostics): the library records the name and an
+ * instance tag of every kernel launch of the calling thread in a thread-local
+ * ring (the last 64 launches; host-side only, no HIP call).  i counts from 0
+ * at the first launch since jabd_launch_log_reset(); the name is a static
+ * string, NULL (and tag 0) when i is outside the kept range.  The conv
+ * families' tags: conv1x1_m32 (all forms), conv1x1, conv_gemm and
+ * conv3x3_tile 100 * TM + TN; conv1x1_m32s 100 * KS + TN; conv1x1_stream
+ * 100 * KC + TN; other kernels 0. */
+int jabd_launch_log_reset(void);
+int64_t jabd_launch_log_count(void);
+const char* jabd_launch_log_name(int32_t i);
+int jabd_launch_log_tag(int32_t i);
+
 /* ------------------------------------------------------------------------ *
  * A6/A10 box decoding — utils/utils_bbox.py:29-34 (decode) and :39-46
  * (decode_landm).  loc [B,A,4], landm [B,A,10], priors [A,4] (cx,cy,w,h).
@@ -368,7 +381,10 @@ typedef struct jabd_conv_args {
    * fixed-order reduction (deterministic).  NULL: no split. */
   void* ws; int64_t ws_bytes;
 } jabd_conv_args;
-/* Workspace bytes jabd_conv2d_nhwc_f32 can use for args (0: it would not split). */
+/* Workspace bytes jabd_conv2d_nhwc_f32 can use for args (0: it would not
+ * split).  args as for the launch itself (ws / ws_bytes are not read): the
+ * query follows the launch's own routing and grid, so it is > 0 exactly for
+ * the layers that split when given the workspace. */
 int64_t jabd_conv_workspace_size(const jabd_conv_args* args);
 /* N-tiles (16 output channels each) grouped per workgroup for a Cout. */
 int jabd_conv_pack_tn(int cout);

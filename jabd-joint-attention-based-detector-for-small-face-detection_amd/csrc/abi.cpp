@@ -12,7 +12,30 @@ void set_error(const char* fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
 }
+
+thread_local LaunchLog g_launch_log = {};
 }  // namespace jabd
+
+extern "C" int jabd_launch_log_reset(void) {
+  jabd::g_launch_log.count = 0;
+  return JABD_OK;
+}
+
+extern "C" int64_t jabd_launch_log_count(void) { return jabd::g_launch_log.count; }
+
+// i counts launches since the reset; only the last kLaunchLogCap are kept
+static bool launch_log_kept(int32_t i) {
+  const int64_t n = jabd::g_launch_log.count;
+  return i >= 0 && i < n && i >= n - jabd::kLaunchLogCap;
+}
+
+extern "C" const char* jabd_launch_log_name(int32_t i) {
+  return launch_log_kept(i) ? jabd::g_launch_log.name[i & (jabd::kLaunchLogCap - 1)] : nullptr;
+}
+
+extern "C" int jabd_launch_log_tag(int32_t i) {
+  return launch_log_kept(i) ? jabd::g_launch_log.tag[i & (jabd::kLaunchLogCap - 1)] : 0;
+}
 
 extern "C" const char* jabd_version(void) { return "jabd-mi355x 0.1.0 (gfx950)"; }
 

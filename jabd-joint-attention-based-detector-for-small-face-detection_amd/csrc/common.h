@@ -17,7 +17,25 @@ inline hipStream_t as_stream(jabd_stream_t s) {
   return reinterpret_cast<hipStream_t>(s);
 }
 
-inline int check_launch(const char* what) {
+// Launch witness: the names (string literals) and tags of this thread's last
+// kLaunchLogCap kernel launches, so a test can tell which kernel instance
+// produced an output (jabd_launch_log_*, abi.cpp).  Host-side only: one
+// pointer store, one int store and one increment per launch.
+constexpr int kLaunchLogCap = 64;
+struct LaunchLog {
+  const char* name[kLaunchLogCap];
+  int tag[kLaunchLogCap];
+  int64_t count;
+};
+extern thread_local LaunchLog g_launch_log;
+
+// tag: the instance the launcher picked (conv families: INTEGRATION.md), 0 elsewhere
+inline int check_launch(const char* what, int tag = 0) {
+  LaunchLog& l = g_launch_log;
+  const int slot = (int)(l.count & (kLaunchLogCap - 1));
+  l.name[slot] = what;
+  l.tag[slot] = tag;
+  ++l.count;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("%s: %s", what, hipGetErrorString(e));

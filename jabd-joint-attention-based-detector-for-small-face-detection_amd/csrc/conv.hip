@@ -677,7 +677,7 @@ static int launch_conv3x3_tile(const ConvArgs& a, hipStream_t st) {
 #define C3_CASE(TN_, TM_)                                                                    \
   if (tn == TN_ && tm == TM_) {                                                              \
     conv3x3_tile_kernel<TN_, TM_><<<(unsigned)grid, 256, lds, st>>>(a, tiles_w, tiles_img);  \
-    return check_launch("conv3x3_tile");                                                     \
+    return check_launch("conv3x3_tile", 100 * TM_ + TN_);                                    \
   }
   C3_CASE(1, 2) C3_CASE(2, 2) C3_CASE(3, 2) C3_CASE(1, 4) C3_CASE(2, 4) C3_CASE(3, 4)
 #undef C3_CASE
@@ -693,7 +693,7 @@ static int launch_1x1(const ConvArgs& a, hipStream_t st) {
 #define C1_CASE(X2_, AS_)                                                    \
   if (x2 == X2_ && as == AS_) {                                              \
     conv1x1_kernel<TM, TN, X2_, AS_><<<(unsigned)grid, 256, 0, st>>>(a);     \
-    return check_launch("conv1x1");                                          \
+    return check_launch("conv1x1", 100 * TM + TN);                           \
   }
   C1_CASE(0, false) C1_CASE(0, true) C1_CASE(1, false) C1_CASE(1, true)
   C1_CASE(2, false) C1_CASE(2, true)
@@ -712,7 +712,7 @@ static int launch_conv(const ConvArgs& a, bool vec4, hipStream_t st) {
     conv_gemm_kernel<TM, TN, true><<<(unsigned)grid, 256, 0, st>>>(a);
   else
     conv_gemm_kernel<TM, TN, false><<<(unsigned)grid, 256, 0, st>>>(a);
-  return check_launch("conv_gemm");
+  return check_launch("conv_gemm", 100 * TM + TN);
 }
 
 }  // namespace jabd
@@ -760,6 +760,7 @@ namespace jabd {
 bool stem7_ok(const ConvArgs& a);
 int stem7_fwd_launch(const ConvArgs& a, hipStream_t st);
 int conv1x1_m32_dispatch(const ConvArgs& a, hipStream_t st, bool kxk);
+int64_t conv_m32_workspace_bytes(const ConvArgs& a, bool kxk);
 int conv_m32_stats_dispatch(const ConvArgs& a, bool kxk, float* part, const BnEpi& bb,
                             hipStream_t st);
 int64_t bn_rows_sum_doubles(int64_t M, int C);
@@ -847,6 +848,29 @@ static int conv_setup(const jabd_conv_args* args, ConvArgs& a, bool& fast1x1, bo
                                      a.x2_bs * a.B < ((int64_t)1 << 31)))) &&
       (a.M + 64) * (maxps + 16) < ((int64_t)1 << 31) && !conv_generic_only();
   return 0;
+}
+
+// Whether jabd_conv2d_nhwc_f32 hands the layer to the 32x32 tile GEMM
+// (conv1x1_m32_dispatch): 0 no, 1 its 1x1 form, 2 its k x k implicit GEMM
+// (32-channel stages inside one tap).  jabd_conv_workspace_size asks the same
+// question, so a split-K workspace is sized for exactly the layers that split.
+static int conv_m32_route(const ConvArgs& a, bool fast1x1, bool vec4) {
+  const bool is1x1 = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
+  const int64_t OHW = (int64_t)a.OH * a.OW;
+  if (is1x1) return fast1x1 && use_conv32(a) ? 1 : 0;
+  const bool kxk = vec4 && (a.flags & 1) && !a.x2 && !a.y2 && a.Cin % 32 == 0 &&
+                   (!a.tconv || a.stride == 1 || (a.stride == 2 && !a.ascale)) &&
+                   a.x_bs % 4 == 0 && a.y_bs == OHW * a.y_ps &&
+                   (!a.res || a.res_bs == OHW * a.res_ps) && use_conv32(a);
+  return kxk ? 2 : 0;
+}
+
+extern "C" int64_t jabd_conv_workspace_size(const jabd_conv_args* args) {
+  ConvArgs a;
+  bool fast1x1 = false, vec4 = false;
+  if (!args || conv_setup(args, a, fast1x1, vec4) != JABD_OK) return 0;
+  const int route = conv_m32_route(a, fast1x1, vec4);
+  return route ? conv_m32_workspace_bytes(a, route == 2) : 0;
 }
 
 // The statistics form of the streaming 1x1 conv serves the layer iff the
@@ -1050,7 +1074,8 @@ extern "C" int jabd_conv2d_nhwc_f32(const jabd_conv_args* args, jabd_stream_t st
   if (stem7_on && stem7_ok(a) && (a.flags & 1) && (a.act == ACT_NONE || a.act == ACT_RELU) &&
       a.Ntiles >= 4 && !conv_generic_only())
     return stem7_fwd_launch(a, st);
-  if (fast1x1 && use_conv32(a)) {
+  const int m32 = conv_m32_route(a, fast1x1, vec4);
+  if (m32 == 1) {
     const int r = conv1x1_m32_dispatch(a, st, false);
     if (r >= 0) return r;
   }
@@ -1059,9 +1084,7 @@ extern "C" int jabd_conv2d_nhwc_f32(const jabd_conv_args* args, jabd_stream_t st
     if (r >= 0) return r;
   }
   // k x k implicit GEMM on the 32x32 kernel: 32-channel stages inside one tap
-  if (!is1x1 && vec4 && (a.flags & 1) && !a.x2 && !a.y2 && a.Cin % 32 == 0 &&
-      (!a.tconv || a.stride == 1 || (a.stride == 2 && !a.ascale)) && a.x_bs % 4 == 0 &&
-      a.y_bs == OHW * a.y_ps && (!a.res || a.res_bs == OHW * a.res_ps) && use_conv32(a)) {
+  if (m32 == 2) {
     const int r = conv1x1_m32_dispatch(a, st, true);
     if (r >= 0) return r;
   }

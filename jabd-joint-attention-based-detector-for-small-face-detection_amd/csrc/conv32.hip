@@ -685,7 +685,7 @@ __global__ __launch_bounds__(256) void conv1x1_m32s_kernel(const ConvArgs p, int
 // at bs1: enough splits for ~512 workgroups, each keeping >= 4 stages of 32
 // channels; 1 = no split.  Needs a caller workspace (args.ws).
 static int m32_ksplit(const ConvArgs& a, bool kxk, int64_t grid) {
-  if (a.tconv || a.Cout % 4 || grid >= 256) return 1;
+  if (a.tconv || a.Cout % 4 || a.Cin % kBK || grid >= 256) return 1;
   const int Kt = kxk ? a.KH * a.KW * a.Cin : a.Cin + (a.x2 ? a.Cin2 : 0);
   const int S = (Kt + kBK - 1) / kBK;
   int ks = (int)std::min<int64_t>(8, (512 + grid - 1) / grid);
@@ -694,6 +694,15 @@ static int m32_ksplit(const ConvArgs& a, bool kxk, int64_t grid) {
 }
 static int64_t m32_ksplit_bytes(const ConvArgs& a, int ks) {
   return ks > 1 ? (int64_t)ks * a.B * a.OH * a.OW * a.ntiles32 * 32 * (int64_t)sizeof(float) : 0;
+}
+// Workgroups of a plain (non-phase) launch with TM x TN wave tiles: M is tiled
+// per image under the ECA gate, flat otherwise.  The launch and the workspace
+// query (conv_m32_workspace_bytes) both take the grid from here.
+static int64_t m32_grid(const ConvArgs& a, int TM, int TN) {
+  const int64_t BM = 4 * 32 * TM;
+  const int64_t OHW = (int64_t)a.OH * a.OW;
+  const int64_t mtiles = a.ascale ? cdiv(OHW, BM) * a.B : cdiv(a.M, BM);
+  return mtiles * (a.ntiles32 / TN);
 }
 
 template <int TM, int TN, bool KXK, bool AS>
@@ -722,19 +731,18 @@ static int launch_m32_as(const ConvArgs& a, hipStream_t st) {
         conv1x1_m32_kernel<TM, TN, KXK, AS><<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, 0,
                                                                         2 * ph + pw, 1, nullptr,
                                                                         BnEpi{});
-        if (int e = check_launch("conv1x1_m32")) return e;
+        if (int e = check_launch("conv1x1_m32", 100 * TM + TN)) return e;
       }
     return JABD_OK;
   }
-  const int64_t mtiles = per_img ? mt_img * a.B : cdiv(a.M, BM);
-  const int64_t grid = mtiles * (a.Ntiles / TN);
+  const int64_t grid = m32_grid(a, TM, TN);  // (a.Ntiles == a.ntiles32 here)
   JABD_REQUIRE(grid < (int64_t)0x7fffffff, "conv32: grid too large");
   const int ks = a.ws ? m32_ksplit(a, KXK, grid) : 1;
   if (ks > 1 && a.ws_bytes >= m32_ksplit_bytes(a, ks)) {
     float* part = static_cast<float*>(a.ws);
     conv1x1_m32_kernel<TM, TN, KXK, AS><<<dim3((unsigned)grid, (unsigned)ks), 256, 0, st>>>(
         a, (int)mt_img, per_img, -1, ks, part, BnEpi{});
-    if (int e = check_launch("conv1x1_m32 (split K)")) return e;
+    if (int e = check_launch("conv1x1_m32 (split K)", 100 * TM + TN)) return e;
     const int64_t n4 = a.M * ((a.Cout + 3) / 4);
     m32_ksplit_reduce<<<(unsigned)cdiv(n4, 256), 256, 0, st>>>(a, ks, part);
     return check_launch("m32_ksplit_reduce");
@@ -747,12 +755,12 @@ static int launch_m32_as(const ConvArgs& a, hipStream_t st) {
       else
         conv1x1_m32_kernel<1, TN, KXK, false, false, false, kEpiNone>
             <<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1, 1, nullptr, BnEpi{});
-      return check_launch("conv1x1_m32");
+      return check_launch("conv1x1_m32", 100 * TM + TN);
     }
   }
   conv1x1_m32_kernel<TM, TN, KXK, AS><<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1,
                                                                      1, nullptr, BnEpi{});
-  return check_launch("conv1x1_m32");
+  return check_launch("conv1x1_m32", 100 * TM + TN);
 }
 
 // conv1x1_m32s_kernel launch: a persistent grid of (CUs x resident
@@ -784,7 +792,7 @@ static int launch_m32s(const ConvArgs& a, float* part, const BnEpi& bb, hipStrea
   int64_t gm = std::min<int64_t>(cdiv(ntiles, 4), slots / nblk_n);
   gm = std::max<int64_t>(8, gm / 8 * 8);  // whole XCD rounds (see the kernel)
   kern<<<(unsigned)(gm * nblk_n), 256, lds, st>>>(a, nblk_n, part, bb);
-  return check_launch("conv1x1_m32s");
+  return check_launch("conv1x1_m32s", 100 * KS + TN);
 }
 
 // The streaming form for a 1x1 / stride-1 layer with K = 64 or 128 (a: the
@@ -852,11 +860,11 @@ static int launch_m32_stats(const ConvArgs& a, float* part, const BnEpi& bb, hip
   if (bb.rows) {
     conv1x1_m32_kernel<1, TN, KXK, false, false, true><<<(unsigned)grid, 256, 0, st>>>(
         a, (int)cdiv((int64_t)a.OH * a.OW, 128), 0, -1, 1, nullptr, bb);
-    return check_launch("conv1x1_m32 (BN backward sums)");
+    return check_launch("conv1x1_m32 (BN backward sums)", 100 + TN);
   }
   conv1x1_m32_kernel<1, TN, KXK, false, true><<<(unsigned)grid, 256, 0, st>>>(
       a, (int)cdiv((int64_t)a.OH * a.OW, 128), 0, -1, 1, part, BnEpi{});
-  return check_launch("conv1x1_m32 (BN statistics)");
+  return check_launch("conv1x1_m32 (BN statistics)", 100 + TN);
 }
 
 int conv_m32_stats_dispatch(const ConvArgs& a0, bool kxk, float* part, const BnEpi& bb,
@@ -919,24 +927,26 @@ static int m32_tn_launch(const ConvArgs& a) {
   return mtiles * (a.ntiles32 / a.tn32) >= 256 ? a.tn32 : 1;
 }
 
-// N-tiles (32 output channels each) per workgroup for the 32x32 kernel.
-// Prefers a 64x128 wave tile (TM=2, TN<=4), else the exact-fit wide tile.
-extern "C" int64_t jabd_conv_workspace_size(const jabd_conv_args* args) {
-  if (!args) return 0;
-  const ConvArgs& a = *args;
-  if (!a.w32 || a.Cin % 32 || a.tconv || a.nchw_in || a.tn32 <= 0) return 0;
-  // 1x1 / stride 1 / pad 0 takes the 32x32 kernel's 1x1 form, anything else its k x k form
-  const bool kxk = !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0);
-  ConvArgs am = a;
-  am.M = (int64_t)a.B * a.OH * a.OW;
-  const int tn = m32_tn_launch(am);
-  const int TM = tn == a.tn32 ? m32_tm(am) : 1;
-  const int64_t BM = 4 * 32 * TM;
-  const int64_t OHW = (int64_t)a.OH * a.OW;
-  const int64_t mtiles = a.ascale ? cdiv(OHW, BM) * a.B : cdiv((int64_t)a.B * OHW, BM);
-  const int64_t grid = mtiles * (a.ntiles32 / tn);
-  return m32_ksplit_bytes(a, m32_ksplit(a, kxk, grid));
+// The wave tiles (tm x tn) conv1x1_m32_dispatch launches a layer with: one
+// N-tile under the small-grid override, else the packing's tn32 at m32_tm.
+static void m32_tile(const ConvArgs& a, int& tm, int& tn) {
+  tn = m32_tn_launch(a);
+  tm = (tn == 1 && a.tn32 > 1) ? 1 : m32_tm(a);
 }
+
+namespace jabd {
+// Split-K workspace bytes of a layer (a.M set) that jabd_conv2d_nhwc_f32
+// routes to conv1x1_m32_dispatch(a, st, kxk); 0: no split.  The tile choice,
+// the grid and the split come from the helpers the launch itself uses, so
+// the query (jabd_conv_workspace_size, conv.hip) and the launch cannot drift.
+// (K 64 / 128 1x1 layers on the streaming form have <= 4 stages: no split.)
+int64_t conv_m32_workspace_bytes(const ConvArgs& a, bool kxk) {
+  if (!a.w32 || a.tn32 <= 0 || a.tn32 > 7 || a.tconv || a.nchw_in) return 0;
+  int tm, tn;
+  m32_tile(a, tm, tn);
+  return m32_ksplit_bytes(a, m32_ksplit(a, kxk, m32_grid(a, tm, tn)));
+}
+}  // namespace jabd
 
 extern "C" int jabd_conv_pack_tn32(int cout) {
   const int nt = (cout + 31) / 32;
@@ -962,29 +972,15 @@ int conv1x1_m32_dispatch(const ConvArgs& a0, hipStream_t st, bool kxk) {
     const int r = m32s_dispatch(a, a0.tn32, nullptr, BnEpi{}, 0, st);
     if (r >= 0) return r;
   }
-#define M32(TM_, TN_) \
-  return kxk ? launch_m32<TM_, TN_, true>(a, st) : launch_m32<TM_, TN_, false>(a, st);
-  if (m32_tn_launch(a0) == 1 && a0.tn32 > 1) M32(1, 1)
-  if (m32_tm(a0) == 1) {
-    switch (a0.tn32) {
-      case 1: M32(1, 1)
-      case 2: M32(1, 2)
-      case 3: M32(1, 3)
-      case 4: M32(1, 4)
-      default: break;
-    }
-  }
-  switch (a0.tn32) {
-    case 1: M32(2, 1)
-    case 2: M32(2, 2)
-    case 3: M32(2, 3)
-    case 4: M32(2, 4)
-    case 5: M32(1, 5)
-    case 6: M32(1, 6)
-    case 7: M32(1, 7)
-    default: return -1;
-  }
+  int tm, tn;
+  m32_tile(a0, tm, tn);
+#define M32(TM_, TN_)         \
+  if (tm == TM_ && tn == TN_) \
+    return kxk ? launch_m32<TM_, TN_, true>(a, st) : launch_m32<TM_, TN_, false>(a, st);
+  M32(1, 1) M32(1, 2) M32(1, 3) M32(1, 4) M32(2, 1) M32(2, 2) M32(2, 3) M32(2, 4)
+  M32(1, 5) M32(1, 6) M32(1, 7)
 #undef M32
+  return -1;
 }
 }  // namespace jabd
 

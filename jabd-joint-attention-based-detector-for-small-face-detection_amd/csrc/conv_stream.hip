@@ -330,7 +330,7 @@ int conv1x1_stream_dispatch(const ConvArgs& a, hipStream_t st, StreamStats* ss) 
     const int grid = stream_grid(kern, nw_ * 64, lds, cdiv(nblk, nw_));                     \
     if (grid < 1) return -1;                                                                \
     kern<<<grid, nw_ * 64, lds, st>>>(a, (int)nblk, (int)ohw, nullptr, nullptr);            \
-    return check_launch("conv1x1_stream");                                                  \
+    return check_launch("conv1x1_stream", 100 * KC_ + TN_);                                 \
   } while (0)
 #define CS_LAUNCH_ST(TN_, KC_)                                                              \
   do {                                                                                      \
@@ -347,7 +347,7 @@ int conv1x1_stream_dispatch(const ConvArgs& a, hipStream_t st, StreamStats* ss) 
                  "conv1x1_bn_stats: %lld partial rows given, kernel grid %d",               \
                  (long long)ss->nblk, grid);                                                \
     kern<<<grid, nw_ * 64, lds, st>>>(a, (int)nblk, (int)ohw, ss->part, ss->shift);         \
-    return check_launch("conv1x1_stream_stats");                                            \
+    return check_launch("conv1x1_stream_stats", 100 * KC_ + TN_);                           \
   } while (0)
 #define CS_FLAGS_ST(TN_, KC_) \
   if (ss && TN == TN_ && KC == KC_) CS_LAUNCH_ST(TN_, KC_);

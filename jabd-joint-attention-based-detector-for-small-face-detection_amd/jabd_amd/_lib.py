@@ -105,6 +105,10 @@ SIGNATURES = {
     "jabd_version": [],
     "jabd_abi_struct_size": [c_i32],
     "jabd_last_error": [ctypes.c_char_p, c_size],
+    "jabd_launch_log_reset": [],
+    "jabd_launch_log_count": [],
+    "jabd_launch_log_name": [c_i32],
+    "jabd_launch_log_tag": [c_i32],
     "jabd_decode_f32": [c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_vp, c_vp],
     "jabd_decode_landm_f32": [c_vp, c_vp, c_i64, c_i64, c_f32, c_vp, c_vp],
     "jabd_nms_workspace_size": [c_i64, c_i64, c_sizep],
@@ -285,6 +289,7 @@ SIGNATURES = {
                                    c_i32, c_vp, c_vp],
 }
 _RESTYPE = {"jabd_version": ctypes.c_char_p, "jabd_dw_nblk": ctypes.c_int64,
+            "jabd_launch_log_count": ctypes.c_int64, "jabd_launch_log_name": ctypes.c_char_p,
             "jabd_expand_dw_nblk": ctypes.c_int64,
             "jabd_bn_nblk": ctypes.c_int64, "jabd_conv_wgrad_part_floats": ctypes.c_int64,
             "jabd_conv_wgrad_eca_part_floats": ctypes.c_int64, "jabd_bn_sum_nblk": ctypes.c_int64,
@@ -334,6 +339,21 @@ def call(name, *args):
     st = getattr(lib(), name)(*args)
     if st != 0:
         raise RuntimeError(f"{name} failed (status {st}): {last_error()}")
+
+
+def launch_log_reset():
+    lib().jabd_launch_log_reset()
+
+
+def launch_log():
+    """[(kernel name, instance tag)] of the calling thread's launches since
+    launch_log_reset() (the launch witness; the library keeps the last 64)."""
+    h = lib()
+    out = []
+    for i in range(int(h.jabd_launch_log_count())):
+        name = h.jabd_launch_log_name(i)
+        out.append((name.decode() if name is not None else None, int(h.jabd_launch_log_tag(i))))
+    return out
 
 
 def exported_symbols():

@@ -109,7 +109,11 @@ def test_stem_parity(cuda, act, hw):
 def test_conv3x3_tile_parity(cuda, cin, cout, split, hw, gate):
     """The LDS-tiled 3x3 / stride-1 kernel (conv3x3_tile_kernel: SSH branches,
     FPN merges) vs torch fp32 conv2d: ragged tiles, the ECA gate applied while
-    staging, and the split output of the fused SSH branches."""
+    staging, and the split output of the fused SSH branches.  The launch
+    witness must show conv3x3_tile at 2 rows per wave with the packing's TN
+    (tag 200 + jabd_conv_pack_tn(cout): 203, 202, 202, 203, 201) in every
+    case; Cin 64 -> 48 stays off the 32x32 GEMM because Cout < 64."""
+    from jabd_amd import _lib
     from jabd_amd import functional as F
     H, W = hw
     g = torch.Generator().manual_seed(cin * 7 + cout + H)
@@ -127,34 +131,60 @@ def test_conv3x3_tile_parity(cuda, cin, cout, split, hw, gate):
     pk = F.pack_conv(conv.to(cuda))
     xg = x.permute(0, 2, 3, 1).contiguous().to(cuda)
     asc = sc.to(cuda).contiguous() if gate else None
+    _lib.launch_log_reset()
     if split:
         y = torch.empty((B, H, W, split), device=cuda)
         y2 = torch.empty((B, H, W, cout - split), device=cuda)
         F.conv(xg, pk, pad=1, act="relu", ascale=asc, out=y, y2=y2, nsplit=split,
                act2="leaky", slope2=0.1)
+        log = _lib.launch_log()
         got = torch.cat([y, y2], -1).permute(0, 3, 1, 2).cpu()
         want = torch.cat([tF.relu(ref[:, :split]), tF.leaky_relu(ref[:, split:], 0.1)], 1)
     else:
-        got = F.conv(xg, pk, pad=1, act="relu", ascale=asc).permute(0, 3, 1, 2).cpu()
+        y = F.conv(xg, pk, pad=1, act="relu", ascale=asc)
+        log = _lib.launch_log()
+        got = y.permute(0, 3, 1, 2).cpu()
         want = tF.relu(ref)
+    assert log == [("conv3x3_tile", 200 + pk.tn)], log
     assert rel_err(got, want) < 2e-5, rel_err(got, want)
+
+
+# (cin, cin2, hw) of test_conv1x1_stream_parity's cases -> the kernel and instance tag
+# the launch witness must show (conv1x1: 100 TM + TN; conv1x1_stream: 100 KC + TN)
+STREAM_PARITY_KERNEL = {
+    (16, 0, (33, 31)): ("conv1x1", 101), (64, 16, (17, 23)): ("conv1x1", 102),
+    (72, 0, (16, 16)): ("conv1x1_stream", 502), (120, 0, (8, 40)): ("conv1x1_stream", 803),
+    (40, 0, (31, 7)): ("conv1x1_stream", 303), (200, 0, (12, 13)): ("conv1x1", 105),
+    (240, 40, (5, 9)): ("conv1x1", 105),
+}
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("cin,cin2,cout,gate,res,hw,act", [
-    (16, 0, 16, True, True, (33, 31), "relu"),      # KC 1, ragged last block
-    (64, 16, 24, True, False, (17, 23), "relu"),    # K-concat skip source (b2)
-    (72, 0, 24, True, True, (16, 16), "relu"),      # KC 5 with a half stage (b3)
-    (120, 0, 40, True, True, (8, 40), "hswish"),    # KC 8, TN 3 (b5)
-    (40, 0, 40, False, False, (31, 7), "leaky"),    # FPN lateral
-    (200, 0, 80, True, True, (12, 13), "hswish"),   # 8-wave workgroups (b8)
-    (240, 40, 80, True, False, (5, 9), "hswish"),   # KC 18 + K-concat (b7)
+    # gated with OH * OW % 16 != 0: conv1x1_stream_dispatch returns -1 and conv.hip's
+    # conv1x1_kernel runs
+    (16, 0, 16, True, True, (33, 31), "relu"),      # conv1x1 TN 1: b1's shape, ragged map
+    (64, 16, 24, True, False, (17, 23), "relu"),    # conv1x1 TN 2: K-concat skip source (b2)
+    # the streaming kernel
+    (72, 0, 24, True, True, (16, 16), "relu"),      # stream: KC 5 with a half stage (b3)
+    (120, 0, 40, True, True, (8, 40), "hswish"),    # stream: KC 8, TN 3 (b5)
+    (40, 0, 40, False, False, (31, 7), "leaky"),    # stream: FPN lateral, M % 16 != 0
+    # gated with OH * OW % 16 != 0 again
+    (200, 0, 80, True, True, (12, 13), "hswish"),   # conv1x1 TN 5: b8's shape, ragged map
+    (240, 40, 80, True, False, (5, 9), "hswish"),   # conv1x1 TN 5: b7's shape + K-concat
 ])
 def test_conv1x1_stream_parity(cuda, cin, cin2, cout, gate, res, hw, act):
-    """The streaming 1x1 kernel (conv_stream.hip: persistent workgroups, LDS
-    weights + gates, next block's K stages in flight) vs torch fp32: ragged
+    """The 1x1 kernels of the short-K / narrow-N layers vs torch fp32: the
+    streaming kernel (conv_stream.hip: persistent workgroups, LDS weights +
+    gates, next block's K stages in flight) where it serves the layer, and
+    conv.hip's conv1x1_kernel on the gated maps whose pixel count is not a
+    multiple of 16 (the 840^2 training maps 105^2, 53^2, 27^2 in production);
+    STREAM_PARITY_KERNEL names the kernel the launch witness must show.  Ragged
     pixel counts, half-filled K stages, the K-concatenated skip source, the
-    ECA gate on the first source only, residual and activation."""
+    ECA gate on the first source only, residual and activation.  (The
+    streaming kernel's K-concat and 8-wave forms: tests/test_conv_dispatch.py
+    cases s-v.)"""
+    from jabd_amd import _lib
     from jabd_amd import functional as F
     H, W = hw
     B = 3
@@ -182,8 +212,11 @@ def test_conv1x1_stream_parity(cuda, cin, cin2, cout, gate, res, hw, act):
         conv.bias.copy_(b)
     pk = F.pack_conv(conv.to(cuda), extra=extra)
     nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous().to(cuda)  # noqa: E731
-    y = F.conv(nhwc(x), pk, act=act, slope=0.1, ascale=sc.to(cuda).contiguous() if gate else None,
-               x2=nhwc(x2) if cin2 else None, res=nhwc(r) if res else None)
+    xg, x2g, rg = nhwc(x), nhwc(x2) if cin2 else None, nhwc(r) if res else None
+    asc = sc.to(cuda).contiguous() if gate else None
+    _lib.launch_log_reset()
+    y = F.conv(xg, pk, act=act, slope=0.1, ascale=asc, x2=x2g, res=rg)
+    assert _lib.launch_log() == [STREAM_PARITY_KERNEL[(cin, cin2, hw)]]
     got = y.permute(0, 3, 1, 2).cpu()
     assert rel_err(got, want) < 2e-5, rel_err(got, want)
 

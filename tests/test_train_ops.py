@@ -581,8 +581,16 @@ def test_conv1x1_stream32_forms(cuda, cin, cout, bhw):
     epilogue forms against float64 torch: plain (no terms), bias + ReLU
     (run-time epilogue), a data gradient with the residual, the BatchNorm
     statistics form and the BatchNorm-backward sums form; ragged last tiles,
-    one pixel, and N not a multiple of 128 (TN 1-3)."""
+    one pixel, and N not a multiple of 128 (TN 1-3).  The launch witness must
+    show conv1x1_m32s (tag 100 KS + TN, TN halved until KS * TN <= 8) for the
+    plain and the bias + ReLU call; 64 -> 32 is below use_conv32's Cout >= 64
+    and really runs conv1x1_stream (KC 4, TN 2)."""
+    from jabd_amd import _lib
     from jabd_amd import train as T
+    kern = {(64, 256): ("conv1x1_m32s", 204), (64, 64): ("conv1x1_m32s", 202),
+            (128, 512): ("conv1x1_m32s", 402), (64, 96): ("conv1x1_m32s", 203),
+            (128, 128): ("conv1x1_m32s", 402), (64, 32): ("conv1x1_stream", 402),
+            (128, 256): ("conv1x1_m32s", 402)}[(cin, cout)]
     B, H, W = bhw
     g = torch.Generator().manual_seed(cin * 7 + cout)
     x = (torch.randn(B, H, W, cin, generator=g) + 1.0) * 3.0
@@ -593,13 +601,17 @@ def test_conv1x1_stream32_forms(cuda, cin, cout, bhw):
     xg, wg, bg, rg = x.to(dev), w.to(dev), b.to(dev), r.to(dev)
     ref = x.double().reshape(-1, cin) @ w.double().reshape(cout, cin).t()
     ref = ref.reshape(B, H, W, cout)
+    _lib.launch_log_reset()
     y0 = T._conv_fwd(xg, wg, None, 1, 0)
+    assert [e for e in _lib.launch_log() if e[0] != "conv_pack"] == [kern]   # (+ the weight pack)
     pk = T._packed(wg, transposed=False)
     a = T._conv_args(xg, pk, torch.empty(B, H, W, cout, device=dev), 1, 0)
     a.bias, a.act = bg.data_ptr(), T.ACT["relu"]   # bias + ReLU: the run-time epilogue
     yb = torch.empty(B, H, W, cout, device=dev)
     a.y = yb.data_ptr()
+    _lib.launch_log_reset()
     T.call("jabd_conv2d_nhwc_f32", T.ctypes.byref(a), T._st())
+    assert _lib.launch_log() == [kern]
     bn = torch.nn.BatchNorm2d(cout).to(dev)
     ys, st = T._conv_fwd_stats(xg, wg, bn, 1, 0)
     # data gradient cout <- cin with the residual (the R50 conv1 data gradient's form)
