@@ -1476,18 +1476,28 @@ class R50BlockFn(torch.autograd.Function):
         H, W = ctx.hw
         x, t1p, t1, t2p, t2, t3p, idn, *sv = ctx.saved_tensors
         st1, st2, st3 = ctx.st
-        dout = dout.contiguous()
         info = ctx.info
-        if info is not None and info["rows"] is not None and info["dz"] == dout.data_ptr():
+        rows = None
+        if info is not None and info["rows"] is not None:
+            # taken only when the incoming gradient IS the tensor the next
+            # block wrote, untouched: the record is used once (a second
+            # backward over a retained graph writes a new one), and a tensor
+            # the engine accumulated another consumer's gradient into in place
+            # has a bumped version (same pointer, other values)
+            dz = info["dz"]()
+            if dz is not None and dout is dz and dout._version == info["dz_version"]:
+                rows = info["rows"]
+                LINKS_TAKEN[0] += 1
+            info["rows"] = info["dz"] = None
+        dout = dout.contiguous()
+        if rows is not None:
             # the next block's conv1 data gradient already wrote dz = dout *
             # [out > 0] and bn3's sums: only the apply pass is left, and dz
             # is the identity branch's gradient
-            dp3, dg3, db3, _ = _bn_bwd_rows(dout, t3p, st3, "none", info["rows"])
+            dp3, dg3, db3, _ = _bn_bwd_rows(dout, t3p, st3, "none", rows)
             dres = dout
         else:
             dp3, dg3, db3, dres = _bn_bwd(dout, t3p, st3, "relu", res=idn, want_dres=True)
-        if info is not None:
-            info.clear()
         dW3 = _wgrad(t2, dp3, blk.conv3.weight, 1, 0)
         # the data-gradient GEMMs also take the next BatchNorm backward's sums
         dt2, pt2 = _dgrad_bn_sums(dp3, blk.conv3.weight, 1, 0, t2.shape[1], t2.shape[2], t2p,
@@ -1510,12 +1520,19 @@ class R50BlockFn(torch.autograd.Function):
         else:
             ds_skip = dres
         prev = ctx.prev
-        if prev is not None and prev.get("x3") is not None:
+        rows = None
+        # (an observed x — retain_grad() or a tensor hook — must see its true
+        # gradient, so it gets the plain data gradient)
+        if prev is not None and prev.get("x3") is not None and not x.retains_grad and \
+                not getattr(x, "_backward_hooks", None):
             dx, rows = _dgrad_1x1_res_bn3(dp1, blk.conv1.weight, ds_skip, x, prev["x3"],
                                           prev["st3"])
-            prev["rows"], prev["dz"] = rows, (dx.data_ptr() if rows is not None else None)
         else:
             dx = _dgrad_1x1_res(dp1, blk.conv1.weight, ds_skip)
+        if rows is not None:
+            prev.update(rows=rows, dz=weakref.ref(dx), dz_version=dx._version)
+        elif prev is not None:
+            prev["rows"] = prev["dz"] = None
         return (None, None, None, dx) + grads
 
 
@@ -1543,17 +1560,28 @@ R50_FUSED = __import__("os").environ.get("JABD_R50_FUSED", "1") != "0"
 # (jabd_bn_act_bwd_ex_f32's two passes) instead of from the dz + sums the
 # next bottleneck's conv1 data gradient writes (A/B)
 R50_BN3_LINK = __import__("os").environ.get("JABD_R50_BN3_LINK", "1") != "0"
+# bn3 backwards taken from a link since import (tests assert that the default
+# training path still takes them)
+LINKS_TAKEN = [0]
 
 
-def _r50_block(blk, x):
+def _r50_block(blk, x, link=False):
+    """link: the caller vouches that this block's output feeds the next
+    bottleneck and nothing else (the _train_forward chain), so that block's
+    conv1 data gradient may hand this one dz + bn3's sums in place of the true
+    gradient of the output (R50_BN3_LINK).  Being the same object is not
+    enough: a second consumer of the output, retain_grad() or a hook on it
+    would all see or alter dz.  Off, the block takes bn3's backward from dout
+    (drop-in modules, direct callers)."""
     if _r50_fused_ok(blk, x):
         x = x.contiguous()
-        # link to the producing bottleneck when x IS its output object (its
-        # only consumer is this block: the _train_forward chain; a fork or
-        # any other use gives a different object)
-        rec = getattr(x, "_jabd_r50_link", None) if R50_BN3_LINK else None
+        link = link and R50_BN3_LINK
+        # link to the producing bottleneck when it offered one and x IS its
+        # output object; R50BlockFn.backward still checks that the gradient
+        # it receives is the linked tensor, unmodified
+        rec = getattr(x, "_jabd_r50_link", None) if link else None
         prev = rec[1] if rec is not None and rec[0]() is x else None
-        info = {} if R50_BN3_LINK else None
+        info = {} if link else None
         out = R50BlockFn.apply(blk, prev, info, x, *_r50_params(blk))
         if info is not None:
             out._jabd_r50_link = (weakref.ref(out), info)
@@ -1776,7 +1804,9 @@ def _train_forward(model, kind, x):
     feats = []
     for i in (1, 2, 3, 4):
         for blk in getattr(body, f"layer{i}"):
-            s = _r50_block(blk, s)
+            # the chain is single-consumer: every use of a stage output
+            # besides the next bottleneck goes through fork() below
+            s = _r50_block(blk, s, link=True)
         if i in (2, 3):  # feeds the next stage and the FPN
             s, f = fork(s, 2)
             feats.append(f)
