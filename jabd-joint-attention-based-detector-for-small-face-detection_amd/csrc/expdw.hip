@@ -20,6 +20,8 @@
 // in registers across the switch).  Workgroup ids are decoded XCD-aware: the
 // EC-chunks of one tile land on the same XCD (id % 8), so their re-reads of
 // the input tile hit that XCD's L2.
+#include <type_traits>
+
 #include "expdw_shared.h"
 
 namespace jabd {
@@ -30,7 +32,7 @@ namespace jabd {
 template <int K, int S, int TH, int TW, int EC, bool SKIP, int NW, int SKC>
 constexpr int xd1_min_wg() {
   using C = XdCfg<K, S, TH, TW, EC>;
-  constexpr int bytes = C::LDS * 4 + K * K * (EC / 4) * 16 + (SKIP ? 10 * (SKC / 4) * 16 : 16);
+  constexpr int bytes = C::LDS * 4 + (K * K + 1) * (EC / 4) * 16 + (SKIP ? 10 * (SKC / 4) * 16 : 16);
   return (SKIP && NW == 4 && 4 * bytes <= 160 * 1024) ? 4 : 2;
 }
 
@@ -59,10 +61,10 @@ __global__ __launch_bounds__(64 * NW, (xd1_min_wg<K, S, TH, TW, EC, SKIP, NW, SK
   constexpr int NPF = (C::IPAD * 4 + T - 1) / T;
   constexpr int BPW = (C::NBLK + NW - 1) / NW;  // MFMA blocks per wave
   static_assert(NW % C::NNT == 0, "waves split evenly over the 16-channel tiles");
-  constexpr int NWD = K * K * C::NC4;  // depthwise taps staged in LDS (bias: registers)
+  constexpr int NWD = (K * K + 1) * C::NC4;  // depthwise taps and bias (row K * K) staged in LDS
   // skip-branch taps staged in LDS (SKC >= Cin), none without the skip branch
   __shared__ __attribute__((aligned(16))) float lds[C::LDS];
-  __shared__ float4 wsh[K * K][C::NC4];
+  __shared__ float4 wsh[K * K + 1][C::NC4];
   __shared__ float4 sws[SKIP ? 10 : 1][SKIP ? SKC / 4 : 1];  // 9 taps + bias of the skip dw
   XdItem it;
   XD_RT(0);
@@ -96,15 +98,15 @@ __global__ __launch_bounds__(64 * NW, (xd1_min_wg<K, S, TH, TW, EC, SKIP, NW, SK
   float4 pwd = make_float4(0.f, 0.f, 0.f, 0.f);
   if (t < NWD) {
     const int tp = t / C::NC4, cc = it.c0 + 4 * (t - tp * C::NC4);
-    const float4 w = *reinterpret_cast<const float4*>(p.wd + tp * p.E + (cc < p.E ? cc : 0));
+    const float4 w = *reinterpret_cast<const float4*>((tp < K * K ? p.wd + tp * p.E : p.bd) +
+                                                      (cc < p.E ? cc : 0));
     pwd = cc < p.E ? w : make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  // depthwise lane map and its bias (consumed after the expand phase)
+  // depthwise lane map
   int c4, sl;
   dw_lane<C::NC4>(lane, c4, sl);
   const int chl = 4 * c4;
   const bool chv = it.c0 + chl < p.E;
-  const float4 bias2 = *reinterpret_cast<const float4*>(p.bd + (chv ? it.c0 + chl : 0));
   // PRE: packed project weights of lane (j, g) (component e: input channel
   // 4g + e, output channel j) scaled by this image's gate; bias of output
   // channels 4g .. 4g + 3 (the lane's accumulator rows)
@@ -123,26 +125,38 @@ __global__ __launch_bounds__(64 * NW, (xd1_min_wg<K, S, TH, TW, EC, SKIP, NW, SK
   // stage slot u of this thread: pixel u*16*NW + (t>>6)*16 + (t&15), channel quad (t>>4)&3
   const int cq = ((t >> 4) & 3) * 4;
   const int spx0 = (t >> 6) * 16 + (t & 15);
-  // KP-deep register ring of input stages: stage kc + KP is issued as soon
-  // as stage kc has been written to LDS, and the raw LDS barriers below keep
-  // it in flight across the MFMA phase (a __syncthreads() would drain it).
-  float4 pf[KP][NPF];
-  auto load_stage = [&](int kc, float4 (&dst)[NPF]) {
-    const int cofs = 16 * kc + cq;
-    const uint32_t base = (uint32_t)(it.b * p.x_bs + cofs);
-    const bool cok = cofs < p.Cin;
+  // byte offset of slot u at stage 0, decoded once per workgroup (a stage
+  // adds its 64 bytes); XD_OOR outside the tile / the image
+  constexpr uint32_t XD_OOR = 0xFFFFFFF0u;
+  uint32_t soff[NPF];
+  {
+    const uint32_t base = (uint32_t)(it.b * p.x_bs + cq);
 #pragma unroll
     for (int u = 0; u < NPF; ++u) {
       const int px = u * 16 * NW + spx0;
       const int r = px / C::IW, c = px - r * C::IW;
       const int ih = it.ih0 + r, iw = it.iw0 + c;
-      const bool ok = px < C::IPX && cok &&
+      const bool ok = px < C::IPX &&
                       (interior || ((unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W));
-      const uint32_t off = ok ? (base + (uint32_t)((ih * p.W + iw) * p.x_ps)) * 4u : 0xFFFFFFF0u;
+      soff[u] = ok ? (base + (uint32_t)((ih * p.W + iw) * p.x_ps)) * 4u : XD_OOR;
+    }
+  }
+  // KP-deep register ring of input stages: stage kc + KP is issued as soon
+  // as stage kc has been written to LDS, and the raw LDS barriers below keep
+  // it in flight across the MFMA phase (a __syncthreads() would drain it).
+  float4 pf[KP][NPF];
+  auto load_stage = [&](int kc, float4 (&dst)[NPF]) {
+    const bool cok = 16 * kc + cq < p.Cin;
+#pragma unroll
+    for (int u = 0; u < NPF; ++u) {
+      // one select, no branch: a branch here would wait for the loads in flight
+      const bool ok = (int)cok & (int)(soff[u] != XD_OOR);
+      const uint32_t off = ok ? soff[u] + 64u * (uint32_t)kc : XD_OOR;
       if (XD_SKIP & 16) dst[u] = make_float4(0.f, 0.f, 0.f, (float)off);
       else dst[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0));
     }
   };
+  typedef decltype(__builtin_amdgcn_raw_buffer_load_b128(xr, 0u, 0, 0)) b128_t;
   // accumulators start at the expand bias (no epilogue add)
   f32x4 acc[BPW];
   const f32x4 bias4 = (f32x4){pbi.x, pbi.y, pbi.z, pbi.w};
@@ -160,6 +174,15 @@ __global__ __launch_bounds__(64 * NW, (xd1_min_wg<K, S, TH, TW, EC, SKIP, NW, SK
   // sum over k is taken in another order.  (Cin 40 with a run-time stage
   // count measured +5% on the 3x3/s2 skip form: not taken there.)
   const bool tail8 = KCC == 2 && (p.Cin & 15) == 8;
+  // PRE: the residual tile.  Slot u of the stage is pixel 16 (wave + NW u) + j,
+  // channels 4g .. 4g + 3: the lane's project accumulator rows of pixel block
+  // wave + NW u, and the residual has x's strides, so soff[u] addresses it
+  // too.  Issued with the d tile (after the weight load, so that retiring
+  // that load leaves these in flight) instead of after the first barrier: one
+  // HBM round trip per tile, not two in series.
+  constexpr int BPP = (C::NPB + NW - 1) / NW;
+  static_assert(!PRE || BPP == NPF, "PRE: one stage slot per project block");
+  float4 res[PRE ? BPP : 1];
   for (int kc0 = 0; kc0 < Kc; kc0 += KP) {
 #pragma unroll
     for (int s = 0; s < KP; ++s) {
@@ -173,6 +196,14 @@ __global__ __launch_bounds__(64 * NW, (xd1_min_wg<K, S, TH, TW, EC, SKIP, NW, SK
         a = (f32x4){wf[0], wf[64], 0.f, 0.f};
       } else {
         a = wpk[(kc * p.Ntiles + ntc) * 64 + lane];
+      }
+      if constexpr (PRE) {
+        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(p.pres), (short)0, (int)(uint32_t)((int64_t)p.B * p.x_bs * 4),
+            0x00020000);
+#pragma unroll
+        for (int u = 0; u < BPP; ++u)
+          res[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rr, soff[u], 0, 0));
       }
 #pragma unroll
       for (int u = 0; u < NPF; ++u) {
@@ -192,24 +223,14 @@ __global__ __launch_bounds__(64 * NW, (xd1_min_wg<K, S, TH, TW, EC, SKIP, NW, SK
         // the same quad planes (lane (j, g) of block pb: pixel 16 pb + j,
         // channels 4g .. 4g + 3); zero outside the image (the expand input's
         // padding) and on the pad pixels past IPX
-        constexpr int BPP = (C::NPB + NW - 1) / NW;
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.pres), (short)0, (int)(uint32_t)((int64_t)p.B * p.x_bs * 4),
-            0x00020000);
+        // A lane reads only the LDS slot it then overwrites (plane g, pixel
+        // 16 pb + j), so no barrier separates the reads of d from the writes
+        // of the block output.
         f32x4 pacc[BPP];
-        float4 res[BPP];
-        bool pin[BPP];
 #pragma unroll
         for (int u = 0; u < BPP; ++u) {
           const int pb = wave + NW * u;
           const int px = pb * 16 + j;
-          const int r = px / C::IW, c = px - r * C::IW;
-          const int ih = it.ih0 + r, iw = it.iw0 + c;
-          pin[u] = pb < C::NPB && px < C::IPX &&
-                   (interior || ((unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W));
-          const uint32_t off =
-              pin[u] ? (uint32_t)(it.b * p.x_bs + (ih * p.W + iw) * p.x_ps + 4 * g) * 4u : 0xFFFFFFF0u;
-          res[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rr, off, 0, 0));
           pacc[u] = (f32x4){bpre.x, bpre.y, bpre.z, bpre.w};
           if (pb < C::NPB) {
             const f32x4 bv = *reinterpret_cast<const f32x4*>(lds + (g * C::IPAD + px) * 4);
@@ -219,7 +240,6 @@ __global__ __launch_bounds__(64 * NW, (xd1_min_wg<K, S, TH, TW, EC, SKIP, NW, SK
             pacc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(apre.w, bv.w, pacc[u], 0, 0, 0);
           }
         }
-        lds_barrier();  // every wave's reads of d done
 #pragma unroll
         for (int u = 0; u < BPP; ++u) {
           const int pb = wave + NW * u;
@@ -228,7 +248,7 @@ __global__ __launch_bounds__(64 * NW, (xd1_min_wg<K, S, TH, TW, EC, SKIP, NW, SK
                                  pacc[u][2] + res[u].z, pacc[u][3] + res[u].w);
           if (p.pact == ACT_RELU) v = xd_act4<ACT_RELU>(v);
           else if (p.pact == ACT_HSWISH) v = xd_act4<ACT_HSWISH>(v);
-          if (!pin[u]) v = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (soff[u] == XD_OOR) v = make_float4(0.f, 0.f, 0.f, 0.f);  // outside the image / pad pixel
           *reinterpret_cast<float4*>(lds + (g * C::IPAD + pb * 16 + j) * 4) = v;
         }
         lds_barrier();
@@ -255,8 +275,13 @@ __global__ __launch_bounds__(64 * NW, (xd1_min_wg<K, S, TH, TW, EC, SKIP, NW, SK
               const float4 wv = sws[kh * 3 + kw][sq];
               v = fma4pk(xv, wv, v);
             }
-          *reinterpret_cast<float4*>(p.sy + (int64_t)it.b * p.sy_bs +
-                                     ((int64_t)oh * p.OW + ow) * p.sy_ps + sc) = v;
+          const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
+              p.sy + (int64_t)it.b * p.sy_bs, (short)0,
+              (int)(((uint32_t)(p.OH * p.OW - 1) * (uint32_t)p.sy_ps + (uint32_t)p.Cin) * 4u),
+              0x00020000);
+          __builtin_amdgcn_raw_buffer_store_b128(
+              __builtin_bit_cast(b128_t, v), sr,
+              (uint32_t)((oh * p.OW + ow) * p.sy_ps + sc) * 4u, 0, 0);
         }
       }
       // a wave whose 16-channel tile lies past E skips its MFMAs (wave-uniform;
@@ -329,43 +354,69 @@ __global__ __launch_bounds__(64 * NW, (xd1_min_wg<K, S, TH, TW, EC, SKIP, NW, SK
   constexpr int SPW = 64 / C::NC4;  // strips per wave per pass
   float4 psum = make_float4(0.f, 0.f, 0.f, 0.f);
   if (chv && !(XD_SKIP & 4)) {
-    float* yb = p.y + (int64_t)it.b * p.y_bs + it.c0 + chl;
+    // y goes through a buffer descriptor of this image, as the input does:
+    // 32-bit offsets stepped along a strip instead of a 64-bit address per
+    // store (host: an image of y < 4 GiB); the range ends at the last
+    // pixel's last channel
+    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
+        p.y + (int64_t)it.b * p.y_bs, (short)0,
+        (int)(((uint32_t)(p.OH * p.OW - 1) * (uint32_t)p.y_ps + (uint32_t)p.E) * 4u), 0x00020000);
+    const float4 bias2 = wsh[K * K][c4];
+    // A thread's strips are NW * SPW apart: RPP rows down in the same strip
+    // column, so the row, the LDS row pointer and the output offset are
+    // decoded once and stepped per pass.  A tile that lies whole inside the
+    // output map (workgroup-uniform, most tiles) takes the path with no
+    // per-output bounds.
+    static_assert((NW * SPW) % C::NSTRIP == 0, "a pass covers whole tile rows");
+    constexpr int RPP = NW * SPW / C::NSTRIP;  // tile rows per pass
+    const int strip0 = wave * SPW + sl;
+    const int orow0 = strip0 / C::NSTRIP, st = strip0 - orow0 * C::NSTRIP;
+    const int owb = it.ow0 + st * C::PW;
+    const float* rowp0 = lds + (c4 * C::QP + orow0 * S * C::IW + st * C::PW * S) * 4;
+    const uint32_t ystep = (uint32_t)p.y_ps * 4u;
+    const uint32_t yoff0 = ((uint32_t)((it.oh0 + orow0) * p.OW + owb) * (uint32_t)p.y_ps +
+                            (uint32_t)(it.c0 + chl)) * 4u;
+    auto dw_phase = [&](auto fullc) {
+      constexpr bool FULL = decltype(fullc)::value;
+      const float* rowq = rowp0;
+      uint32_t yoff = yoff0;
 #pragma unroll 1
-    for (int pass = 0; pass * T < C::ITEMS; ++pass) {
-      const int strip = (pass * NW + wave) * SPW + sl;
-      if (strip >= TH * C::NSTRIP) break;
-      const int orow = strip / C::NSTRIP, st = strip - orow * C::NSTRIP;
-      const int oh = it.oh0 + orow, owb = it.ow0 + st * C::PW;
-      if (oh >= p.OH || owb >= p.OW) continue;
-      float4 a2[C::PW];
+      for (int orow = orow0; orow < TH;
+           orow += RPP, rowq += RPP * S * C::IW * 4, yoff += (uint32_t)RPP * p.OW * ystep) {
+        if (!FULL && (it.oh0 + orow >= p.OH || owb >= p.OW)) continue;
+        float4 a2[C::PW];
 #pragma unroll
-      for (int o = 0; o < C::PW; ++o) a2[o] = bias2;
+        for (int o = 0; o < C::PW; ++o) a2[o] = bias2;
 #pragma unroll 1
-      for (int kh = 0; kh < K; ++kh) {
-        const float* rowp = lds + (c4 * C::QP + (orow * S + kh) * C::IW + st * C::PW * S) * 4;
-        float4 row[C::SPAN];
+        for (int kh = 0; kh < K; ++kh) {
+          const float* rowp = rowq + kh * C::IW * 4;
+          float4 row[C::SPAN];
 #pragma unroll
-        for (int c = 0; c < C::SPAN; ++c)
-          row[c] = *reinterpret_cast<const float4*>(rowp + c * 4);
-        float4 wk[K];
+          for (int c = 0; c < C::SPAN; ++c)
+            row[c] = *reinterpret_cast<const float4*>(rowp + c * 4);
+          float4 wk[K];
 #pragma unroll
-        for (int kw = 0; kw < K; ++kw) wk[kw] = wsh[kh * K + kw][c4];
+          for (int kw = 0; kw < K; ++kw) wk[kw] = wsh[kh * K + kw][c4];
 #pragma unroll
-        for (int o = 0; o < C::PW; ++o)
+          for (int o = 0; o < C::PW; ++o)
 #pragma unroll
-          for (int kw = 0; kw < K; ++kw) {
-            const float4 xv = row[o * S + kw], wv = wk[kw];
-            a2[o] = fma4pk(xv, wv, a2[o]);
-          }
+            for (int kw = 0; kw < K; ++kw) {
+              const float4 xv = row[o * S + kw], wv = wk[kw];
+              a2[o] = fma4pk(xv, wv, a2[o]);
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < C::PW; ++o) {
+          if (!FULL && owb + o >= p.OW) break;
+          const float4 v = xd_act4<ACT>(a2[o]);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(b128_t, v), yr,
+                                                 yoff + (uint32_t)o * ystep, 0, 0);
+          psum.x += v.x; psum.y += v.y; psum.z += v.z; psum.w += v.w;
+        }
       }
-#pragma unroll
-      for (int o = 0; o < C::PW; ++o) {
-        if (owb + o >= p.OW) break;
-        const float4 v = xd_act4<ACT>(a2[o]);
-        *reinterpret_cast<float4*>(yb + ((int64_t)oh * p.OW + owb + o) * p.y_ps) = v;
-        psum.x += v.x; psum.y += v.y; psum.z += v.z; psum.w += v.w;
-      }
-    }
+    };
+    if (it.oh0 + TH <= p.OH && it.ow0 + TW <= p.OW) dw_phase(std::true_type{});
+    else dw_phase(std::false_type{});
   }
   XD_T(5);
   if (p.part && !(XD_SKIP & 8)) {
@@ -1245,6 +1296,10 @@ extern "C" int jabd_expand_dw_nhwc_f32(const jabd_expdw_args* args, jabd_stream_
                   make_fastdiv((uint32_t)tiles_w)};
   JABD_REQUIRE((int64_t)a.B * a.x_bs * 4 < ((int64_t)1 << 32) - 16,
                "expand_dw: input must be < 4 GiB (buffer-descriptor offsets)");
+  // the outputs are stored through one buffer descriptor per image
+  JABD_REQUIRE((int64_t)a.OH * a.OW * a.y_ps * 4 < ((int64_t)1 << 32) &&
+                   (!a.sy || (int64_t)a.OH * a.OW * a.sy_ps * 4 < ((int64_t)1 << 32)),
+               "expand_dw: one image of the output must be < 4 GiB");
   if (a.pw) {  // the previous block's project fused in front (one form)
     JABD_REQUIRE(a.pb && a.pg && a.pres && a.pg_bs >= a.Cin &&
                      (a.pact == ACT_NONE || a.pact == ACT_RELU || a.pact == ACT_HSWISH),
