@@ -1,6 +1,7 @@
-// Shared device code of the fused expand + depthwise kernels (expdw.hip:
-// expdw1 / strip / wave-specialised forms and the dispatcher; expdw2.hip:
-// the persistent default form).
+// Device helpers of the fused expand + depthwise kernels in expdw.hip: the
+// default kernel (expdw1_kernel) and its bit-for-bit witness, the
+// wave-specialised form (expdw_ws_kernel).  Tile geometry, item decode, LDS
+// barrier, activations, depthwise lane map and the timing-experiment hooks.
 #pragma once
 #include <stdlib.h>
 
@@ -11,12 +12,10 @@ namespace jabd {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Phase-skip mask for timing experiments only (tools/xd_variant.sh builds
-// libraries with -DXD_SKIP=n; results are wrong): 1 expand MFMAs, 2 expanded-
-// tile LDS writes, 4 depthwise phase, 8 ECA reduce, 16 input loads;
-// expdw_ws_kernel: 32 expand-wave MFMAs, 64 depthwise-wave depthwise phase,
-// 128 expand-wave input loads (out-of-range offsets: zeros, no traffic), 256
-// expand-wave epilogue (activation + expanded-tile writes).
+// Phase-skip mask of expdw1_kernel for timing experiments only
+// (tools/xd_variant.sh builds libraries with -DXD_SKIP=n; results are wrong):
+// 1 expand MFMAs, 2 expanded-tile LDS writes, 4 depthwise phase, 8 ECA reduce,
+// 16 input loads.
 #ifndef XD_SKIP
 #define XD_SKIP 0
 #endif
@@ -202,13 +201,5 @@ struct XdTile {
 };
 XdTile xd_tile(int k, int s);
 int xd_skc(int cin);
-// expdw2.hip: launch the persistent form for this geometry (JABD_EINVAL when
-// no instantiation covers it; the caller then uses expdw1_kernel)
-int expdw2_dispatch(const jabd_expdw_args& a, const XdDivs& dv, int64_t nitems, int EC, int nch,
-                    hipStream_t st);
-// expdw3.hip: the chunk-pipelined persistent form for input-narrow layers
-// (JABD_EINVAL when it does not cover the geometry; the caller falls back)
-int expdw3_dispatch(const jabd_expdw_args& a, const XdDivs& dv, int tiles_img, bool forced,
-                    hipStream_t st);
 
 }  // namespace jabd

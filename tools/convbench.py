@@ -196,9 +196,6 @@ def run_xd(shape, reps):
         skip = (torch.randn(9, cin, device=dev, generator=g) / 3,
                 torch.randn(cin, device=dev, generator=g) * 0.1)
     y, part = F.expand_dw(x, pk, wd, bd, k, stride, act=act, skip=skip)[:2]
-    dbg = int(os.environ.get("XD_DBG", "0"))
-    if dbg:
-        F._XD_DBG = dbg
     fa = torch.relu if act == "relu" else torch.nn.functional.hardswish
     e1 = fa(x.reshape(-1, cin) @ we + be).reshape(B, H, W, E).permute(0, 3, 1, 2)
     r = torch.nn.functional.conv2d(e1, wd.t().reshape(E, 1, k, k), bd, stride, k // 2, 1, E)
