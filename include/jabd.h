@@ -87,8 +87,43 @@ int jabd_batched_nms_f32(const float* boxes, int64_t box_stride,
                          int64_t* keep, int64_t* n_keep, void* ws,
                          size_t ws_bytes, jabd_stream_t stream);
 
-/* Measurement helper: after jabd_batched_nms_f32 with the same (batch, n,
- * ws), copy to host arrays each image's number of exact IoU tests made by
+/* The same pipeline with a choice of suppression rule and a candidate cut.
+ * jabd_batched_nms_f32 is this call with (kind 0, beta1 1.0, top_k 0).
+ *   kind 0  IoU: the rule above.
+ *   kind 1  DIoU-NMS — diounms(boxes, scores, overlap, top_k, beta1) of
+ *           utils/utils_bbox.py:182-258 (utils/box_utils.py:450-526): with i
+ *           the kept (higher-ranked) box and j a later one, in fp32 and in
+ *           the reference's operation order,
+ *             inter = max(min(x2i,x2j) - max(x1i,x1j), 0)
+ *                     * max(min(y2i,y2j) - max(y1i,y1j), 0)
+ *             union = (area_j - inter) + area_i
+ *             d = (cxi - cxj)^2 + (cyi - cyj)^2,  cx = (x1 + x2) / 2
+ *             c = (max(x2i,x2j) - min(x1i,x1j))^2 + (max(y2i,y2j) - min(y1i,y1j))^2
+ *             u = d / c;  beta1 != 1: u = (float)pow((double)u, beta1)
+ *           j is suppressed when (double)(inter / union - u) > iou_threshold.
+ *           beta1 == 1 evaluates no pow and is bit-exact with the reference's
+ *           fp32 values; beta1 must be positive and finite (kind 0 ignores it).
+ *           A NaN value never suppresses, as for kind 0: a NaN coordinate in
+ *           either box, or two boxes that are the same point (c = 0), leave
+ *           both boxes kept.  This is the one departure from the reference,
+ *           whose IoU.le(overlap) drops such a box.
+ *   top_k > 0: after the sort only the first min(candidates, top_k) rows of
+ *           each image take part (the reference's idx[-top_k:]); ties at the
+ *           cut follow the stable order (lower row index first).  top_k <= 0:
+ *           no cut.  Applies to both kinds.
+ * Workspace: jabd_nms_workspace_size (unchanged). */
+int jabd_batched_nms_ex_f32(const float* boxes, int64_t box_stride,
+                            int64_t box_bstride, const float* scores,
+                            int64_t score_stride, int64_t score_bstride,
+                            const int64_t* n_valid, int64_t batch, int64_t n,
+                            double iou_threshold, float score_threshold,
+                            int64_t* keep, int64_t* n_keep, void* ws,
+                            size_t ws_bytes, jabd_stream_t stream, int32_t kind,
+                            double beta1, int64_t top_k);
+
+/* Measurement helper: after jabd_batched_nms_f32 (or jabd_batched_nms_ex_f32,
+ * either kind) with the same (batch, n, ws), copy to host arrays each image's
+ * number of exact IoU (or DIoU) tests made by
  * the grid producer (candidate pairs), its off-block suppressing pairs, and
  * its producer (0 = grid, != 0 = dense: every pair tested).  Synchronises
  * the stream; batch <= 254. */
@@ -126,6 +161,15 @@ int jabd_detect_f32(const float* loc, const float* conf, const float* landm,
                     float var0, float var1, float conf_threshold,
                     double nms_threshold, float* out, int64_t* n_keep,
                     void* ws, size_t ws_bytes, jabd_stream_t stream);
+/* The same with the suppression rule, beta1 and top_k of
+ * jabd_batched_nms_ex_f32 (kind 0 = IoU, 1 = DIoU); jabd_detect_f32 is this
+ * call with (0, 1.0, 0). */
+int jabd_detect_ex_f32(const float* loc, const float* conf, const float* landm,
+                       const float* priors, int64_t batch, int64_t num_priors,
+                       float var0, float var1, float conf_threshold,
+                       double nms_threshold, float* out, int64_t* n_keep,
+                       void* ws, size_t ws_bytes, jabd_stream_t stream,
+                       int32_t kind, double beta1, int64_t top_k);
 
 /* ------------------------------------------------------------------------ *
  * A7/A8 anchor matching + encoding — nets/retinaface_training.py:93-162

@@ -828,11 +828,12 @@ extern "C" int jabd_detect_workspace_size(int64_t batch, int64_t num_priors, siz
   return JABD_OK;
 }
 
-extern "C" int jabd_detect_f32(const float* loc, const float* conf, const float* landm,
-                               const float* priors, int64_t batch, int64_t num_priors,
-                               float var0, float var1, float conf_threshold,
-                               double nms_threshold, float* out, int64_t* n_keep, void* ws,
-                               size_t ws_bytes, jabd_stream_t stream) {
+extern "C" int jabd_detect_ex_f32(const float* loc, const float* conf, const float* landm,
+                                  const float* priors, int64_t batch, int64_t num_priors,
+                                  float var0, float var1, float conf_threshold,
+                                  double nms_threshold, float* out, int64_t* n_keep, void* ws,
+                                  size_t ws_bytes, jabd_stream_t stream, int32_t kind,
+                                  double beta1, int64_t top_k) {
   JABD_REQUIRE(batch >= 0 && num_priors >= 0, "detect: negative size");
   if (batch == 0) return JABD_OK;
   hipStream_t st = as_stream(stream);
@@ -854,11 +855,22 @@ extern "C" int jabd_detect_f32(const float* loc, const float* conf, const float*
       rows);
   if (int e = check_launch("detect_rows")) return e;
   if (int e = nms_core(rows, 15, num_priors * 15, rows + 4, 15, num_priors * 15, nullptr, batch,
-                       num_priors, nms_threshold, conf_threshold, keep, n_keep, nmsws, nws, st))
+                       num_priors, nms_threshold, conf_threshold, keep, n_keep, nmsws, nws, st,
+                       kind, beta1, top_k))
     return e;
   dim3 g((unsigned)cdiv(num_priors, 256), (unsigned)batch);
   gather_rows_kernel<<<g, 256, 0, st>>>(rows, keep, n_keep, num_priors, out);
   return check_launch("detect_gather");
+}
+
+extern "C" int jabd_detect_f32(const float* loc, const float* conf, const float* landm,
+                               const float* priors, int64_t batch, int64_t num_priors,
+                               float var0, float var1, float conf_threshold,
+                               double nms_threshold, float* out, int64_t* n_keep, void* ws,
+                               size_t ws_bytes, jabd_stream_t stream) {
+  return jabd_detect_ex_f32(loc, conf, landm, priors, batch, num_priors, var0, var1,
+                            conf_threshold, nms_threshold, out, n_keep, ws, ws_bytes, stream,
+                            kNmsIoU, 1.0, 0);
 }
 
 static size_t match_ws(int64_t B, int64_t A) {

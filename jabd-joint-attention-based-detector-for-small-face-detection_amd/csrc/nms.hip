@@ -24,6 +24,23 @@
 //                    the kept rows + count.
 // Compile with -ffp-contract=off: IoU must round exactly like the CPU kernel
 // (no FMA in (x2-x1)*(y2-y1) or inter/(a+b-inter)).
+//
+// Two suppression rules share the pipeline; the rule is a compile-time kind
+// of the two mask producers (nms_mask, grid_pairs) and nothing else knows it:
+//   kNmsIoU   torchvision's rule above: IoU(i, j) > thr.
+//   kNmsDIoU  the reference's diounms (utils/utils_bbox.py:182-258,
+//             utils/box_utils.py:450-526): IoU(i, j) - (d / c)^beta1 > thr in
+//             that function's fp32 operation order (diou_gt below), d the
+//             squared centre distance, c the squared diagonal of the enclosing
+//             box, i the kept (lower-rank) box and j the later one — the union
+//             (area_j - inter) + area_i does not round symmetrically.  A NaN
+//             value (a NaN coordinate in either box; two boxes that are the
+//             same point, c = 0) never suppresses, as in the IoU kind.  This
+//             is the one departure from the reference, whose IoU.le(overlap)
+//             drops such a box.
+// Both kinds take a top_k: after the sort only the first min(count, top_k)
+// ranked rows of an image are candidates (the reference's idx[-top_k:]; ties
+// at the cut by the stable order, lower row first); top_k <= 0: no cut.
 #include <math.h>
 #include <stdlib.h>
 
@@ -171,7 +188,7 @@ __global__ void nms_gather(const uint64_t* __restrict__ sorted, int64_t total,
                            int64_t box_bstride, const int* __restrict__ counts,
                            int batch, int64_t n, int img0, float4* __restrict__ sbox,
                            float* __restrict__ sarea, int* __restrict__ sidx,
-                           int* __restrict__ nanflag) {
+                           int* __restrict__ nanflag, int64_t top_k) {
   int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (p >= total) return;
   uint64_t k = sorted[p];
@@ -180,6 +197,7 @@ __global__ void nms_gather(const uint64_t* __restrict__ sorted, int64_t total,
   int64_t start = 0;
   for (int b = 0; b < img; ++b) start += counts[b];
   int64_t r = p - start;
+  if (top_k > 0 && r >= top_k) return;  // past the cut: not a candidate (nms_topk)
   int row = (int)(k & ((1u << kRowBits) - 1));
   const float* bx = boxes + (int64_t)(img + img0) * box_bstride + (int64_t)row * box_stride;
   float x1 = bx[0], y1 = bx[1], x2 = bx[2], y2 = bx[3];
@@ -187,6 +205,13 @@ __global__ void nms_gather(const uint64_t* __restrict__ sorted, int64_t total,
   sarea[(int64_t)img * n + r] = (x2 - x1) * (y2 - y1);
   sidx[(int64_t)img * n + r] = row;
   if (x1 != x1 || y1 != y1 || x2 != x2 || y2 != y2) atomicOr(&nanflag[img], 1);
+}
+
+// top_k: after nms_gather (which locates an image's rows in the sorted keys by
+// the full counts) every image keeps its first min(count, top_k) ranked rows.
+__global__ void nms_topk(int* __restrict__ counts, int batch, int64_t top_k) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < batch && (int64_t)counts[b] > top_k) counts[b] = (int)top_k;
 }
 
 // Per-row sparse suppression lists.  Row i (sorted rank) of row block rb can
@@ -231,14 +256,54 @@ __device__ __forceinline__ bool iou_gt(float ix1, float iy1, float ix2, float iy
   return (double)ovr > thr;
 }
 
+// DIoU(i, j) > thr with the reference's fp32 rounding (diounms, utils/
+// box_utils.py:497-525): bi is the kept box (lower rank), bj the later one.
+// The one exact evaluation of the DIoU kind: both mask producers decide every
+// pair they set with it.  For thr >= 0 a pair whose IoU is clearly at or
+// under the threshold is rejected first: u = (d/c)^beta1 >= 0 (or NaN) and
+// fp32 subtraction of a non-negative value is monotone, so DIoU <= IoU.
+// nan_check: fminf/fmaxf drop a NaN operand where the reference's clamps
+// propagate it (a NaN value never suppresses); images without NaN boxes
+// (nms_gather's nanflag) skip the test.
+__device__ __forceinline__ bool diou_gt(float4 bi, float ai, float4 bj, float aj, double thr,
+                                        float thrf, bool thr_nonneg, bool nan_check,
+                                        double beta1) {
+  if (nan_check && (bi.x != bi.x || bi.y != bi.y || bi.z != bi.z || bi.w != bi.w ||
+                    bj.x != bj.x || bj.y != bj.y || bj.z != bj.z || bj.w != bj.w))
+    return false;
+  const float xx1 = fmaxf(bj.x, bi.x), yy1 = fmaxf(bj.y, bi.y);
+  const float xx2 = fminf(bj.z, bi.z), yy2 = fminf(bj.w, bi.w);
+  const float w = fmaxf(xx2 - xx1, 0.f), h = fmaxf(yy2 - yy1, 0.f);
+  const float inter = w * h;
+  const float uni = (aj - inter) + ai;  // this order: not torchvision's a_i + a_j - inter
+  if (thr_nonneg) {
+    // inter == 0 gives IoU in {0, -0, NaN}: DIoU <= 0 or NaN, never > thr >= 0
+    if (!(inter > 0.f)) return false;
+    if (uni > 1e-30f && uni < 3e38f && inter < thrf * uni * 0.9999f) return false;
+  }
+  const float cxi = (bi.x + bi.z) / 2, cyi = (bi.y + bi.w) / 2;
+  const float cxj = (bj.x + bj.z) / 2, cyj = (bj.y + bj.w) / 2;
+  const float dx = cxi - cxj, dy = cyi - cyj;
+  const float d = dx * dx + dy * dy;
+  const float ex = fmaxf(bj.z, bi.z) - fminf(bj.x, bi.x);
+  const float ey = fmaxf(bj.w, bi.w) - fminf(bj.y, bi.y);
+  const float c = ex * ex + ey * ey;
+  float u = d / c;
+  if (beta1 != 1.0) u = (float)pow((double)u, beta1);
+  const float diou = inter / uni - u;
+  return (double)diou > thr;
+}
+
 // Dense-image tiles (64 rows x kColBlocksPerWG column blocks) as a grid-
 // stride loop over a fixed grid: with no dense image in the batch (the
 // common case) every workgroup leaves after one look at dense[].
+template <int KIND>
 __global__ __launch_bounds__(256) void nms_mask(
     const float4* __restrict__ sbox, const float* __restrict__ sarea,
     const int* __restrict__ counts, int64_t n, int64_t nb, int bc, double thr,
     const int* __restrict__ nanflag, const int* __restrict__ dense, uint64_t* __restrict__ diag,
-    int* __restrict__ nzcnt, int* __restrict__ ent_cb, uint64_t* __restrict__ ent_bits) {
+    int* __restrict__ nzcnt, int* __restrict__ ent_cb, uint64_t* __restrict__ ent_bits,
+    double beta1) {
   __shared__ int any_dense;
   if (threadIdx.x == 0) {
     int a = 0;
@@ -292,7 +357,62 @@ __global__ __launch_bounds__(256) void nms_mask(
     int jstart = (cb == rb) ? lane + 1 : 0;  // strictly after row i on the diagonal
     uint64_t bits = 0;
     if (row_ok) {
-      if (fast) {
+      if (KIND == kNmsDIoU && fast) {
+        // Branch-free screen of the DIoU kind (beta1 == 1): inter, union, d
+        // and c are the exact function's own fp32 values; only the two
+        // quotients come from v_rcp_f32, which is 1 ulp for a denominator in
+        // [1e-30, 1e37] (beyond about 8.5e37 the reciprocal is a denormal and
+        // is flushed to 0: such pairs, like every pair outside okr, go to the
+        // exact function).  Both quotients lie in [0, 4] here, so est is
+        // within 1e-5 of the exact DIoU and a pair more than 1e-4 from the
+        // threshold is decided; the rest (and every pair when beta1 != 1: its
+        // IoU screen alone) goes to the exact function.
+        const float cxi = (bi.x + bi.z) / 2, cyi = (bi.y + bi.w) / 2;
+        const bool b1 = beta1 == 1.0;
+        const float t_hi = thrf + 1e-4f, t_lo = thrf - 1e-4f;
+        uint64_t amb = 0;
+#pragma unroll 8
+        for (int jj = 0; jj < 64; ++jj) {
+          const float4 bj = cbox[lbase + jj];
+          const float aj = carea[lbase + jj];
+          const float xx1 = fmaxf(bj.x, bi.x), yy1 = fmaxf(bj.y, bi.y);
+          const float xx2 = fminf(bj.z, bi.z), yy2 = fminf(bj.w, bi.w);
+          const float w = fmaxf(xx2 - xx1, 0.f), h = fmaxf(yy2 - yy1, 0.f);
+          const float inter = w * h;
+          const float uni = (aj - inter) + ai;
+          const float dx = cxi - (bj.x + bj.z) / 2, dy = cyi - (bj.y + bj.w) / 2;
+          const float d = dx * dx + dy * dy;
+          const float ex = fmaxf(bj.z, bi.z) - fminf(bj.x, bi.x);
+          const float ey = fmaxf(bj.w, bi.w) - fminf(bj.y, bi.y);
+          const float c = ex * ex + ey * ey;
+          const float est = inter * __builtin_amdgcn_rcpf(uni) - d * __builtin_amdgcn_rcpf(c);
+          const bool pos = inter > 0.f;
+          const bool okr = uni > 1e-30f && uni < 1e37f && c > 1e-30f && c < 1e37f &&
+                           inter <= 4.f * uni && d <= 4.f * c;
+          const bool lowiou = okr && inter < thr_lo * uni;  // IoU, hence DIoU, under thr
+          const bool above = b1 && okr && est > t_hi;
+          const bool below = lowiou || (b1 && okr && est < t_lo);
+          const uint64_t bit = (uint64_t)1 << jj;
+          bits |= (pos && above) ? bit : 0ull;
+          amb |= (pos && !above && !below) ? bit : 0ull;
+        }
+        const uint64_t vmask = (jmax >= 64 ? ~0ull : ((1ull << jmax) - 1)) &
+                               ~((jstart >= 64) ? ~0ull : ((1ull << jstart) - 1));
+        bits &= vmask;
+        amb &= vmask;
+        while (amb) {
+          const int jj = __ffsll((unsigned long long)amb) - 1;
+          amb &= amb - 1;
+          if (diou_gt(bi, ai, cbox[lbase + jj], carea[lbase + jj], thr, thrf, true, false, beta1))
+            bits |= (uint64_t)1 << jj;
+        }
+      } else if (KIND == kNmsDIoU) {
+        for (int jj = jstart; jj < jmax; ++jj) {  // NaN image or thr < 0: every pair exact
+          if (diou_gt(bi, ai, cbox[lbase + jj], carea[lbase + jj], thr, thrf, thr_nonneg, true,
+                      beta1))
+            bits |= (uint64_t)1 << jj;
+        }
+      } else if (fast) {
         // Branch-free: fminf/fmaxf equal std::min/max on non-NaN boxes (NaN
         // images take the exact loop below); pairs within 1e-4 of the
         // threshold (or with an out-of-range union) are resolved exactly.
@@ -574,6 +694,7 @@ __global__ void grid_runs_end(const uint64_t* __restrict__ skey, int64_t total,
   tab[h].hi = (int)(p + 1);
 }
 
+template <int KIND>
 __global__ __launch_bounds__(256) void grid_pairs(
     const uint64_t* __restrict__ skey, const int* __restrict__ sval, int64_t total,
     const float4* __restrict__ gbox, int64_t n, int bc,
@@ -582,7 +703,7 @@ __global__ __launch_bounds__(256) void grid_pairs(
     double thr, int* __restrict__ dense, uint64_t* __restrict__ diag,
     uint64_t* __restrict__ rec, int* __restrict__ lcnt, int* __restrict__ wcnt,
     uint64_t* __restrict__ ovf, int* __restrict__ ocnt, int64_t ovcap,
-    unsigned long long* __restrict__ tested) {
+    unsigned long long* __restrict__ tested, double beta1) {
   // XCD-aware block order: hardware block id g runs on XCD g % 8; give each
   // XCD one contiguous eighth of the key order (= one image when the batch
   // holds 8), so an image's candidate arrays stay in one XCD's L2
@@ -702,7 +823,17 @@ __global__ __launch_bounds__(256) void grid_pairs(
 #ifdef JABD_NMS_AB_NOIOU  // A/B timing build: the walk and loads alone (results wrong)
             hit = hit && __float_as_uint(bb[u].x) == 0x7fc00001u && aa_u == 1.f;
 #else
-            if (hit) hit = iou_gt(bi.x, bi.y, bi.z, bi.w, ai, bb[u], aa_u, thr, thrf, true);
+            if (KIND == kNmsDIoU) {
+              // the pair is met once, from either side: the kept box is the
+              // one of lower rank, whichever lane holds it
+              const bool lo = i < j;
+              const float4 brow = lo ? bi : bb[u], bcol = lo ? bb[u] : bi;
+              if (hit)
+                hit = diou_gt(brow, lo ? ai : aa_u, bcol, lo ? aa_u : ai, thr, thrf, true, false,
+                              beta1);
+            } else {
+              if (hit) hit = iou_gt(bi.x, bi.y, bi.z, bi.w, ai, bb[u], aa_u, thr, thrf, true);
+            }
 #endif
 #ifdef JABD_NMS_AB_NOSTORE  // A/B timing build: tests kept, pair output dropped
             ntest += hit ? 65536u : 0u;
@@ -1489,8 +1620,12 @@ int nms_core(const float* boxes, int64_t box_stride, int64_t box_bstride,
              const float* scores, int64_t score_stride, int64_t score_bstride,
              const int64_t* n_valid, int64_t batch, int64_t n, double iou_thr,
              float score_thr, int64_t* keep, int64_t* n_keep, void* ws,
-             size_t ws_bytes, hipStream_t st) {
+             size_t ws_bytes, hipStream_t st, int kind, double beta1, int64_t top_k) {
   JABD_REQUIRE(n >= 0 && batch >= 0, "nms: negative size");
+  JABD_REQUIRE(kind == kNmsIoU || kind == kNmsDIoU, "nms: unknown kind %d", kind);
+  // the grid producer's pruning needs (d/c)^beta1 >= 0
+  JABD_REQUIRE(kind != kNmsDIoU || (beta1 > 0.0 && std::isfinite(beta1)),
+               "nms: beta1 must be positive and finite, got %g", beta1);
   JABD_REQUIRE(n < kMaxRows, "nms: n=%lld exceeds %lld rows per image", (long long)n,
                (long long)kMaxRows);
   const int64_t nb = cdiv(n, 64);
@@ -1565,8 +1700,12 @@ int nms_core(const float* boxes, int64_t box_stride, int64_t box_bstride,
     }
     nms_gather<<<(unsigned)cdiv((int64_t)bc * n, 256), 256, 0, st>>>(
         w.kout, (int64_t)bc * n, boxes, box_stride, box_bstride, w.counts, bc, n, (int)img0,
-        w.sbox, w.sarea, w.sidx, w.nanflag);
+        w.sbox, w.sarea, w.sidx, w.nanflag, top_k);
     if (int e = check_launch("nms_gather")) return e;
+    if (top_k > 0) {
+      nms_topk<<<(unsigned)cdiv((int64_t)bc, 256), 256, 0, st>>>(w.counts, bc, top_k);
+      if (int e = check_launch("nms_topk")) return e;
+    }
     if (grid) {
       dim3 ge((unsigned)cdiv(n, 256 * kExtPer), bc);
       grid_ext<<<ge, 256, 0, st>>>(w.sbox, w.sarea, w.counts, w.nanflag, n, inv_w, w.ext, w.dense,
@@ -1587,10 +1726,11 @@ int nms_core(const float* boxes, int64_t box_stride, int64_t box_bstride,
       if (int e = check_launch("grid_runs_insert")) return e;
       grid_runs_end<<<gt, 256, 0, st>>>(w.kout, (int64_t)bc * n, w.runs, w.run_mask);
       if (int e = check_launch("grid_runs_end")) return e;
-      grid_pairs<<<(unsigned)grid_pair_blocks((int64_t)bc * n), 256, 0, st>>>(
+      (kind == kNmsDIoU ? grid_pairs<kNmsDIoU> : grid_pairs<kNmsIoU>)
+          <<<(unsigned)grid_pair_blocks((int64_t)bc * n), 256, 0, st>>>(
           w.kout, w.gval_out, (int64_t)bc * n, w.gbox, n, bc, inv_w, fcell, w.ext,
           w.runs, w.run_mask, iou_thr, w.dense, w.diag, w.rec, w.lcnt, w.wcnt, w.ovf, w.ocnt,
-          w.ovcap, w.tested);
+          w.ovcap, w.tested, beta1);
       if (int e = check_launch("grid_pairs")) return e;
       const unsigned gk = (unsigned)(w.kchunks * bc);
       const size_t hl = (size_t)nb * sizeof(int);
@@ -1606,8 +1746,9 @@ int nms_core(const float* boxes, int64_t box_stride, int64_t box_bstride,
                                                     w.csr);
       if (int e = check_launch("grid_bucket_scatter")) return e;
     }
-    nms_mask<<<2048, 256, 0, st>>>(w.sbox, w.sarea, w.counts, n, nb, bc, iou_thr, w.nanflag, w.dense,
-                                 w.diag, w.nzcnt, w.ent_cb, w.ent_bits);
+    (kind == kNmsDIoU ? nms_mask<kNmsDIoU> : nms_mask<kNmsIoU>)
+        <<<2048, 256, 0, st>>>(w.sbox, w.sarea, w.counts, n, nb, bc, iou_thr, w.nanflag, w.dense,
+                               w.diag, w.nzcnt, w.ent_cb, w.ent_bits, beta1);
     if (int e = check_launch("nms_mask")) return e;
     if (nb * sizeof(uint64_t) > 64 * 1024) {
       JABD_HIP(hipFuncSetAttribute((const void*)nms_scan,
@@ -1641,6 +1782,23 @@ extern "C" int jabd_nms_workspace_size(int64_t batch, int64_t n, size_t* bytes) 
   return JABD_OK;
 }
 
+extern "C" int jabd_batched_nms_ex_f32(const float* boxes, int64_t box_stride,
+                                       int64_t box_bstride, const float* scores,
+                                       int64_t score_stride, int64_t score_bstride,
+                                       const int64_t* n_valid, int64_t batch, int64_t n,
+                                       double iou_threshold, float score_threshold,
+                                       int64_t* keep, int64_t* n_keep, void* ws,
+                                       size_t ws_bytes, jabd_stream_t stream, int32_t kind,
+                                       double beta1, int64_t top_k) {
+  JABD_REQUIRE(box_stride >= 4 && score_stride >= 1, "nms: bad row stride");
+  JABD_REQUIRE((boxes && scores && keep && n_keep) || n == 0 || batch == 0,
+               "nms: null pointer");
+  JABD_REQUIRE(n_keep || batch == 0, "nms: null n_keep");
+  return jabd::nms_core(boxes, box_stride, box_bstride, scores, score_stride, score_bstride,
+                        n_valid, batch, n, iou_threshold, score_threshold, keep, n_keep, ws,
+                        ws_bytes, jabd::as_stream(stream), kind, beta1, top_k);
+}
+
 extern "C" int jabd_batched_nms_f32(const float* boxes, int64_t box_stride,
                                     int64_t box_bstride, const float* scores,
                                     int64_t score_stride, int64_t score_bstride,
@@ -1648,17 +1806,15 @@ extern "C" int jabd_batched_nms_f32(const float* boxes, int64_t box_stride,
                                     double iou_threshold, float score_threshold,
                                     int64_t* keep, int64_t* n_keep, void* ws,
                                     size_t ws_bytes, jabd_stream_t stream) {
-  JABD_REQUIRE(box_stride >= 4 && score_stride >= 1, "nms: bad row stride");
-  JABD_REQUIRE((boxes && scores && keep && n_keep) || n == 0 || batch == 0,
-               "nms: null pointer");
-  JABD_REQUIRE(n_keep || batch == 0, "nms: null n_keep");
-  return jabd::nms_core(boxes, box_stride, box_bstride, scores, score_stride, score_bstride,
-                        n_valid, batch, n, iou_threshold, score_threshold, keep, n_keep, ws,
-                        ws_bytes, jabd::as_stream(stream));
+  return jabd_batched_nms_ex_f32(boxes, box_stride, box_bstride, scores, score_stride,
+                                 score_bstride, n_valid, batch, n, iou_threshold,
+                                 score_threshold, keep, n_keep, ws, ws_bytes, stream,
+                                 jabd::kNmsIoU, 1.0, 0);
 }
 
 // Measurement helper (bench.py's IoU-pair count): after jabd_batched_nms_f32
-// with this (batch, n, ws), copy each image's number of exact IoU tests of the
+// or jabd_batched_nms_ex_f32 (either kind) with this (batch, n, ws), copy
+// each image's number of exact IoU (or DIoU) tests of the
 // grid producer (candidate pairs), its off-block suppressing pairs, and the
 // producer (0 = grid, != 0 = dense: that image tested every pair) to the host.
 // Synchronises `stream`.  Valid for batch <= 254 (one pass holds every image).

@@ -114,6 +114,9 @@ SIGNATURES = {
     "jabd_nms_workspace_size": [c_i64, c_i64, c_sizep],
     "jabd_batched_nms_f32": [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
                              c_f64, c_f32, c_vp, c_vp, c_vp, c_size, c_vp],
+    "jabd_batched_nms_ex_f32": [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                c_f64, c_f32, c_vp, c_vp, c_vp, c_size, c_vp,
+                                c_i32, c_f64, c_i64],   # kind, beta1, top_k
     "jabd_nms_pair_stats": [c_vp, c_size, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp],
     "jabd_sort_workspace_size": [c_i64, c_i32, c_sizep],
     "jabd_sort_u64": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_size, c_vp],
@@ -122,6 +125,8 @@ SIGNATURES = {
     "jabd_detect_workspace_size": [c_i64, c_i64, c_sizep],
     "jabd_detect_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f64,
                         c_vp, c_vp, c_vp, c_size, c_vp],
+    "jabd_detect_ex_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f64,
+                           c_vp, c_vp, c_vp, c_size, c_vp, c_i32, c_f64, c_i64],
     "jabd_match_workspace_size": [c_i64, c_i64, c_sizep],
     "jabd_match_encode_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_f32, c_f32, c_f32,
                               c_vp, c_vp, c_vp, c_vp, c_size, c_vp],

@@ -73,13 +73,42 @@ def decode_landm(pre, priors, variances):
 
 
 # --------------------------------------------------------------------------- NMS
-def batched_nms(boxes, scores, iou_threshold, score_threshold=-math.inf, n_valid=None):
+_NMS_KINDS = {"iou": 0, "greedynms": 0, "diou": 1, "diounms": 1}
+
+
+def _kind_code(kind, beta1=1.0):
+    """The C-ABI kind (0 = IoU, 1 = DIoU) of a rule name: "iou"/"greedynms" or
+    "diou"/"diounms" (the reference's nms_kind names, utils/utils_bbox.py:309).
+    The DIoU rule needs a positive finite beta1."""
+    try:
+        k = _NMS_KINDS[kind]
+    except (KeyError, TypeError):
+        raise ValueError(f"nms kind must be one of {sorted(_NMS_KINDS)}, got {kind!r}") from None
+    if k == 1 and not (float(beta1) > 0.0 and math.isfinite(float(beta1))):
+        raise ValueError(f"nms: beta1 must be positive and finite, got {beta1!r}")
+    return k
+
+
+def _nms_call(k, beta1, top_k, *args):
+    """jabd_batched_nms_f32 for the default rule, its _ex form otherwise."""
+    if k == 0 and int(top_k) <= 0:
+        call("jabd_batched_nms_f32", *args)
+    else:
+        call("jabd_batched_nms_ex_f32", *args, k, float(beta1), int(top_k))
+
+
+def batched_nms(boxes, scores, iou_threshold, score_threshold=-math.inf, n_valid=None,
+                kind="iou", beta1=1.0, top_k=0):
     """Independent greedy NMS per image.
 
     boxes [B,N,4] (or a [B,N,>=5] row tensor whose first 4 columns are boxes),
     scores [B,N].  Returns (keep [B,N] int64, n_keep [B] int64), both on the
     device; keep[b,:n_keep[b]] are row indices in decreasing-score order.
+    kind "iou"/"greedynms": suppress when IoU > iou_threshold; "diou"/"diounms":
+    when IoU - (d/c)^beta1 > iou_threshold (the reference's diounms).  top_k > 0
+    keeps only each image's top_k best-scored candidates before suppression.
     """
+    k = _kind_code(kind, beta1)
     if boxes.dim() != 3 or boxes.shape[-1] < 4:
         raise ValueError(f"batched_nms: boxes must be [B,N,>=4], got {tuple(boxes.shape)}")
     boxes = _dev("nms.boxes", boxes)
@@ -94,17 +123,18 @@ def batched_nms(boxes, scores, iou_threshold, score_threshold=-math.inf, n_valid
         n_valid = _dev("nms.n_valid", n_valid, torch.int64)
     ws = _ws(_size_query("jabd_nms_workspace_size", B, N), dev)
     C = boxes.shape[-1]
-    call("jabd_batched_nms_f32", _p(boxes), C, N * C, _p(scores), 1, N, _p(n_valid), B, N,
-         float(iou_threshold), float(score_threshold), _p(keep), _p(n_keep), _p(ws),
-         ws.numel(), _stream())
+    _nms_call(k, beta1, top_k, _p(boxes), C, N * C, _p(scores), 1, N, _p(n_valid), B, N,
+              float(iou_threshold), float(score_threshold), _p(keep), _p(n_keep), _p(ws),
+              ws.numel(), _stream())
     return keep, n_keep
 
 
-def batched_nms_stats(boxes, scores, iou_threshold):
+def batched_nms_stats(boxes, scores, iou_threshold, kind="iou", beta1=1.0):
     """batched_nms plus per-image measurement counters: (keep, n_keep,
     tested int64[B], dense bool[B]) where `tested` is the number of exact
-    fp32 IoU evaluations the mask producer made (grid: its candidate pairs;
-    dense: every pair).  Synchronises (measurement only)."""
+    fp32 IoU (or DIoU) evaluations the mask producer made (grid: its candidate
+    pairs; dense: every pair).  Synchronises (measurement only)."""
+    k = _kind_code(kind, beta1)
     B, N = boxes.shape[0], boxes.shape[1]
     dev = boxes.device
     boxes = _dev("nms.boxes", boxes)
@@ -113,9 +143,9 @@ def batched_nms_stats(boxes, scores, iou_threshold):
     n_keep = torch.zeros((B,), dtype=torch.int64, device=dev)
     ws = _ws(_size_query("jabd_nms_workspace_size", B, N), dev)
     C = boxes.shape[-1]
-    call("jabd_batched_nms_f32", _p(boxes), C, N * C, _p(scores), 1, N, None, B, N,
-         float(iou_threshold), float(-math.inf), _p(keep), _p(n_keep), _p(ws), ws.numel(),
-         _stream())
+    _nms_call(k, beta1, 0, _p(boxes), C, N * C, _p(scores), 1, N, None, B, N,
+              float(iou_threshold), float(-math.inf), _p(keep), _p(n_keep), _p(ws), ws.numel(),
+              _stream())
     tested = np.zeros(B, np.int64)
     hits = np.zeros(B, np.int32)
     dense = np.zeros(B, np.int32)
@@ -136,13 +166,16 @@ def nms(boxes, scores, iou_threshold):
     return keep[0, : int(n_keep[0].item())]
 
 
-def detect(loc, conf, landm, priors, variances, conf_threshold=0.5, nms_threshold=0.3):
+def detect(loc, conf, landm, priors, variances, conf_threshold=0.5, nms_threshold=0.3,
+           nms_kind="greedynms", beta1=1.0, top_k=0):
     """predict.py:162-181 on device for a batch: decode + filter + NMS.
 
     loc [B,A,4], conf [B,A,2] (eval softmax), landm [B,A,10].
     Returns (rows [B,A,15], n_keep [B]); rows[b,:n_keep[b]] are the kept
     detections (x1,y1,x2,y2,score,landmarks) in NMS order.
+    nms_kind, beta1, top_k: the suppression rule, as batched_nms.
     """
+    k = _kind_code(nms_kind, beta1)
     loc = _dev("detect.loc", loc)
     conf = _dev("detect.conf", conf)
     landm = _dev("detect.landm", landm)
@@ -154,9 +187,13 @@ def detect(loc, conf, landm, priors, variances, conf_threshold=0.5, nms_threshol
     out = torch.empty((B, A, 15), dtype=torch.float32, device=dev)
     n_keep = torch.empty((B,), dtype=torch.int64, device=dev)   # written by every call
     ws = _ws(_size_query("jabd_detect_workspace_size", B, A), dev)
-    call("jabd_detect_f32", _p(loc), _p(conf), _p(landm), _p(priors), B, A,
-         float(variances[0]), float(variances[1]), float(conf_threshold), float(nms_threshold),
-         _p(out), _p(n_keep), _p(ws), ws.numel(), _stream())
+    args = (_p(loc), _p(conf), _p(landm), _p(priors), B, A,
+            float(variances[0]), float(variances[1]), float(conf_threshold), float(nms_threshold),
+            _p(out), _p(n_keep), _p(ws), ws.numel(), _stream())
+    if k == 0 and int(top_k) <= 0:
+        call("jabd_detect_f32", *args)
+    else:
+        call("jabd_detect_ex_f32", *args, k, float(beta1), int(top_k))
     return out, n_keep
 
 

@@ -1,6 +1,6 @@
 """Box decoding and NMS — drop-in for the reference utils/utils_bbox.py
-(decode :29-34, decode_landm :39-46, non_max_suppression :260-296,
-retinaface_correct_boxes :9-24) with the device work on the HIP path.
+(decode :29-34, decode_landm :39-46, diounms :182-258, non_max_suppression
+:260-296, retinaface_correct_boxes :9-24) with the device work on the HIP path.
 
 `nms` replaces `torchvision.ops.nms` (same signature and result); the
 reference imports it at utils/utils_bbox.py:3.
@@ -45,13 +45,35 @@ def nms(boxes, scores, iou_threshold):
     return ops.nms(boxes, scores, iou_threshold)
 
 
-def non_max_suppression(detection, conf_thres=0.5, nms_thres=0.3):
-    """Score filter + greedy NMS on the device; returns numpy [K,15] or []."""
+def diounms(boxes, scores, overlap=0.5, top_k=200, beta1=1.0):
+    """DIoU-NMS on the device (reference :182-258): boxes [N,4], scores [N].
+    Returns (keep, count) with the reference's contract: keep is an int64
+    tensor of length N, zero past count, and keep[:count] are the kept row
+    indices in decreasing-score order (only the top_k best-scored rows are
+    candidates).  A pair whose DIoU is NaN keeps both boxes."""
+    if boxes.dim() != 2 or boxes.shape[-1] != 4:
+        raise ValueError(f"diounms: boxes must be [N,4], got {tuple(boxes.shape)}")
+    n = boxes.shape[0]
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64, device=boxes.device), 0
+    keep, n_keep = ops.batched_nms(boxes.unsqueeze(0), scores.unsqueeze(0), overlap,
+                                   kind="diou", beta1=beta1, top_k=top_k)
+    count = int(n_keep[0].item())
+    keep = keep[0]
+    keep[count:] = 0
+    return keep, count
+
+
+def non_max_suppression(detection, conf_thres=0.5, nms_thres=0.3, nms_kind="greedynms",
+                        beta1=1.0, top_k=0):
+    """Score filter + NMS (greedy IoU, or "diounms") on the device; returns
+    numpy [K,15] or []."""
     if detection.dim() != 2 or detection.shape[1] < 5:
         raise ValueError("non_max_suppression expects [N, >=5] rows")
     det = detection.contiguous()
     keep, n_keep = ops.batched_nms(det.unsqueeze(0), det[:, 4].contiguous().unsqueeze(0),
-                                   nms_thres, score_threshold=conf_thres)
+                                   nms_thres, score_threshold=conf_thres, kind=nms_kind,
+                                   beta1=beta1, top_k=top_k)
     k = int(n_keep[0].item())
     if k == 0:
         return []
