@@ -2305,10 +2305,16 @@ extern "C" int jabd_bn_act_bwd_ex_f32(const float* dy, int32_t lddy, int32_t dyc
   return check_launch("bn_bwd_apply");
 }
 
+// Launch-witness tag of a tiled weight-gradient launch:
+// family * 1000000 + KT * 1000 + NT.
+enum { kWgTagScalar = 1, kWgTagV = 2, kWgTag32 = 3, kWgTag32Db = 4 };
+static int wgrad_tag(int family, int kt, int nt) { return family * 1000000 + kt * 1000 + nt; }
+
 // The tiled weight-gradient kernels over chunks of `per` output pixels
 // (chunk c covers pixels [c*per, min((c+1)*per, M))), partials part[chunk][K][Cout].
-static void wgrad_launch_parts(const ConvArgs& a, int64_t per, int64_t nch, float* part,
-                               hipStream_t st) {
+// Returns the witness tag of the instance it launched.
+static int wgrad_launch_parts(const ConvArgs& a, int64_t per, int64_t nch, float* part,
+                              hipStream_t st) {
   const int K = a.KH * a.KW * a.Cin;
   const WgDivs dv{make_fastdiv((uint32_t)((int64_t)a.OH * a.OW)), make_fastdiv((uint32_t)a.OW),
                   make_fastdiv((uint32_t)a.Cin), make_fastdiv((uint32_t)a.KW)};
@@ -2328,6 +2334,7 @@ static void wgrad_launch_parts(const ConvArgs& a, int64_t per, int64_t nch, floa
   }
     W32_CASE(64, 64) W32_CASE(64, 128) W32_CASE(128, 64) W32_CASE(128, 128)
 #undef W32_CASE
+    return wgrad_tag(fast ? kWgTag32Db : kWgTag32, tk, tn);
   } else if (wgrad_vec_ok(a)) {
     const int tk = wv_tile(K), tn = wv_tile(a.Cout);
     const int fast = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.H == a.OH &&
@@ -2340,10 +2347,11 @@ static void wgrad_launch_parts(const ConvArgs& a, int64_t per, int64_t nch, floa
     WV_CASE(32, 16) WV_CASE(32, 32) WV_CASE(32, 64)
     WV_CASE(64, 16) WV_CASE(64, 32) WV_CASE(64, 64)
 #undef WV_CASE
-  } else {
-    dim3 g((unsigned)cdiv(K, kWgT), (unsigned)cdiv(a.Cout, kWgT), (unsigned)nch);
-    conv_wgrad_kernel<<<g, 256, 0, st>>>(a, per, part);
+    return wgrad_tag(kWgTagV, tk, tn);
   }
+  dim3 g((unsigned)cdiv(K, kWgT), (unsigned)cdiv(a.Cout, kWgT), (unsigned)nch);
+  conv_wgrad_kernel<<<g, 256, 0, st>>>(a, per, part);
+  return wgrad_tag(kWgTagScalar, kWgT, kWgT);
 }
 
 namespace jabd {
@@ -2423,7 +2431,7 @@ extern "C" int jabd_conv_wgrad_f32(const jabd_conv_args* args, float* part, floa
     const int64_t tot = (int64_t)K * a.Cout;
     wgrad_reduce2_kernel<<<(unsigned)cdiv(tot, 16), 256, 0, st>>>(part, nwv, K, a.Cout, a.Cin,
                                                                   a.KH * a.KW, 16, dw);
-    return check_launch("wgrad_reduce");
+    return check_launch("wgrad_reduce", 16);
   }
   if (stem7_wgrad_on(a)) {
     const int64_t ng = stem7_wgrad_groups(a);
@@ -2431,15 +2439,15 @@ extern "C" int jabd_conv_wgrad_f32(const jabd_conv_args* args, float* part, floa
     const int64_t tot = (int64_t)K * a.Cout;
     wgrad_reduce2_kernel<<<(unsigned)cdiv(tot, 64), 256, 0, st>>>(part, ng, K, a.Cout, a.Cin,
                                                                   a.KH * a.KW, 64, dw);
-    return check_launch("wgrad_reduce");
+    return check_launch("wgrad_reduce", 64);
   }
-  wgrad_launch_parts(a, per, nch, part, st);
-  if (int e = check_launch("conv_wgrad")) return e;
+  const int tag = wgrad_launch_parts(a, per, nch, part, st);
+  if (int e = check_launch("conv_wgrad", tag)) return e;
   const int64_t tot = (int64_t)K * a.Cout;
   const int lanes = tot >= 64 * 512 ? 64 : 16;
   wgrad_reduce2_kernel<<<(unsigned)cdiv(tot, lanes), 256, 0, st>>>(part, nch, K, a.Cout, a.Cin,
                                                                    a.KH * a.KW, lanes, dw);
-  return check_launch("wgrad_reduce");
+  return check_launch("wgrad_reduce", lanes);
 }
 
 // ---------------------------------------------------------------------------
@@ -2557,8 +2565,8 @@ extern "C" int jabd_conv_wgrad_eca_f32(const jabd_conv_args* args, const float* 
   const int64_t nch = cdiv(a.M, per);
   const int cpi = (int)(((int64_t)a.OH * a.OW) / per);
   hipStream_t st = as_stream(stream);
-  wgrad_launch_parts(a, per, nch, part, st);
-  if (int e = check_launch("conv_wgrad")) return e;
+  const int tag = wgrad_launch_parts(a, per, nch, part, st);
+  if (int e = check_launch("conv_wgrad", tag)) return e;
   const int64_t EN = (int64_t)a.Cin * a.Cout;
   float* G = part + nch * EN;
   wgrad_img_reduce_kernel<<<dim3((unsigned)cdiv(EN / 4, 256), (unsigned)a.B), 256, 0, st>>>(

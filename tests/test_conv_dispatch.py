@@ -21,11 +21,16 @@ output, an unwritten output and a write outside [y_c0, y_c0 + Cout) all show.
 (The second source and the residual have no channel offset in
 jabd_amd.functional.conv; every kernel family here takes the x / y windows.)
 
+The training forms (the weight-gradient kernels of jabd_conv_wgrad_f32 and the
+transposed / data-gradient forms of the kernels here) are pinned the same way
+in tests/test_conv_backward_dispatch.py.
+
 Not covered: TM = 4 of conv1x1 / conv_gemm needs more than 262144 pixels at
 K > 400 (a 400 MB case); the JABD_* A/B environment forms (cached per
-process, not product paths); the training forms (tests/test_train_ops.py);
-conv1x1_m32s and conv3x3_tile keep their parity tests in
-tests/test_train_ops.py and tests/test_fused.py, which assert the witness too.
+process, not product paths); the depthwise gradient kernels
+(test_dwconvfn_grads* in tests/test_train_ops.py); conv1x1_m32s and
+conv3x3_tile keep their forward parity tests in tests/test_train_ops.py and
+tests/test_fused.py, which assert the witness too.
 """
 import pytest
 import torch

@@ -294,11 +294,19 @@ def test_wgrad_eca(cuda, B, h, w, E, cout):
     W = torch.randn(cout, E, 1, 1, generator=g, dtype=torch.float64) / E ** 0.5
     dw_ref = torch.einsum("bhwc,bhwn,bc->nc", d, dp, s)
     ds_ref = torch.einsum("bhwn,nc,bhwc->bc", dp, W[:, :, 0, 0], d)
+    from jabd_amd import _lib
+    _lib.launch_log_reset()
     r = _wgrad_eca(d.float().to(cuda), dp.float().to(cuda), W.float().to(cuda),
                    s.float().to(cuda))
+    log = _lib.launch_log()
     assert r is not None
     dw, ds = r
     _check([dw[:, :, 0, 0], ds], [dw_ref, ds_ref], ["dw", "ds"])
+    # the weight-gradient instance (1000000 F + 1000 KT + NT): E < 64 or
+    # cout < 64 -> conv_wgrad_v (F 2), else the double-buffered 32x32 kernel (F 4)
+    tag = {(64, 24): 2064032, (480, 112): 4128064, (672, 160): 4064064, (120, 40): 2064064}
+    assert log == [("conv_wgrad", tag[(E, cout)]), ("wgrad_img_reduce", 0),
+                   ("wgrad_eca_reduce", 0)], log
 
 
 @pytest.mark.gpu
