@@ -28,6 +28,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "conv_args.h"
@@ -76,7 +77,7 @@ template <int TN, bool ST, bool BB, int EPI = kEpiRt>
 __device__ __forceinline__ void m32_epilogue_tm1(const ConvArgs& p, const f32x16 (&acc)[TN],
                                                  int pm, int om, int nb, int srow, float* ep,
                                                  float* __restrict__ part, const BnEpi& bb,
-                                                 int lane) {
+                                                 int lane, int ch0 = 0) {
   const bool has_bias = EPI == kEpiRt && p.bias;
   const bool has_res = EPI == kEpiRes || (EPI == kEpiRt && p.res);
   const int h = lane >> 5, j = lane & 31;
@@ -90,7 +91,7 @@ __device__ __forceinline__ void m32_epilogue_tm1(const ConvArgs& p, const f32x16
   }
 #pragma unroll
   for (int u = 0; u < TN; ++u) {
-    const int nb0 = (nb * TN + u) * 32;
+    const int nb0 = (nb * TN + u) * 32 + ch0;  // (ch0: the 8-wave form's wave half)
     if (nb0 >= p.Cout) break;  // wave-uniform
     const int n = nb0 + 4 * ep_q;
     float4 ss = make_float4(0.f, 0.f, 0.f, 0.f), sq = ss, sh = ss;
@@ -238,7 +239,19 @@ __device__ __forceinline__ void m32_epilogue_tm1(const ConvArgs& p, const f32x16
 // KXK: k x k implicit GEMM (tap-major K; every 32-channel stage lies inside
 // one tap, host guarantees Cin % 32 == 0, no K-concat source); stride-1
 // transposed form (tconv) for the data gradient.
-template <int TM, int TN, bool KXK, bool AS, bool ST = false, bool BB = false, int EPI = kEpiRt>
+// SRC (gated 1x1 launches, the host's choice): what the operand loads may
+// assume.  kSrcRt decides per load at run time where a K group comes from
+// (first / second source at any stride / past K) and whether the gate is
+// applied from global memory (Cin > kGateLds); the compiler then orders the
+// exec-masked loads with waits counted for the longest path, and a wave ends
+// up waiting for a stage's own pixel loads before it issues the weight loads
+// and the stage's MFMAs.  kSrcOne / kSrcTwo: the gate is in LDS and there is
+// no / a stride-1 second source: every load of the next stage is an
+// unconditional load from a clamped address, issued back to back ahead of the
+// stage's MFMAs (a K group past K is zeroed after them).
+enum { kSrcRt = 0, kSrcOne = 1, kSrcTwo = 2 };
+template <int TM, int TN, bool KXK, bool AS, bool ST = false, bool BB = false, int EPI = kEpiRt,
+          int SRC = kSrcRt>
 // AS: the ECA gate (ascale) is set — staged in LDS, applied at the weight store.
 // ST (TM = 1, training forward, no bias / residual / act): the epilogue also
 // writes the following BatchNorm's statistics per 32-pixel wave tile, row
@@ -262,6 +275,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_m32_kernel(const ConvArgs p, i
                                                              int per_img, int phase, int ks,
                                                              float* __restrict__ part,
                                                              const BnEpi bb) {
+  constexpr bool FAST = SRC != kSrcRt;
+  static_assert(!FAST || (AS && !KXK), "SRC: the gated 1x1 forms only");
   constexpr int BM = 4 * 32 * TM;
   constexpr int NB4 = kG * TN * 64;            // float4 of one weight stage
   constexpr int NBT = (NB4 + 255) / 256;       // ... per thread
@@ -301,7 +316,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_m32_kernel(const ConvArgs p, i
     const int m = m_lo + wave * 32 * TM + t * 32 + j;
     pm[t] = m < m_hi ? m : -1;
   }
-  const int Kt = KXK ? nkh * nkw * p.Cin : p.Cin + (p.x2 ? p.Cin2 : 0);
+  const int Kt = KXK ? nkh * nkw * p.Cin
+                     : p.Cin + ((FAST ? SRC == kSrcTwo : p.x2 != nullptr) ? p.Cin2 : 0);
   const int S_all = (Kt + kBK - 1) / kBK;
   const int kchunk = (S_all + ks - 1) / ks;
   const int s_beg = ks > 1 ? (int)blockIdx.y * kchunk : 0;
@@ -330,7 +346,30 @@ __global__ __launch_bounds__(256, 2) void conv1x1_m32_kernel(const ConvArgs p, i
   const float4* wg = reinterpret_cast<const float4*>(p.w);
   const float* sc = AS ? p.ascale + (int64_t)img * p.ascale_bs : nullptr;
 
+  // FAST: the row each lane loads (a row past M reads the tile's first pixel;
+  // its output column is never stored) in the first / second source
+  const float* xa[TM];
+  const float* xb[TM];
+  if constexpr (FAST) {
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+      const int ml = pm[t] >= 0 ? pm[t] : m_lo;
+      xa[t] = p.x + (int64_t)ml * p.x_ps + p.x_c0;
+      xb[t] = SRC == kSrcTwo ? p.x2 + (int64_t)ml * p.x2_ps - p.Cin : xa[t];
+    }
+  }
   auto load_a = [&](int s, float4 (&a)[TM][kG]) {
+    if constexpr (FAST) {
+#pragma unroll
+      for (int t = 0; t < TM; ++t)
+#pragma unroll
+        for (int q = 0; q < kG; ++q) {
+          const int k4 = min(s * kBK + 8 * q + 4 * h, Kt - 4);  // (K % 4 == 0)
+          const float* src = (SRC == kSrcTwo && k4 >= p.Cin) ? xb[t] + k4 : xa[t] + k4;
+          a[t][q] = *reinterpret_cast<const float4*>(src);
+        }
+      return;
+    }
     if constexpr (KXK) {
       const int tl = s / cps, ci0 = (s - tl * cps) * kBK;
       const int khi = tl / nkw;
@@ -379,7 +418,18 @@ __global__ __launch_bounds__(256, 2) void conv1x1_m32_kernel(const ConvArgs p, i
   // store_b applies it on the way to LDS.  Applied in load_b (from global) the
   // multiply makes the wave wait for the weight and gate loads before the
   // stage's MFMAs instead of behind them (b12 project 312 -> see DESIGN).
-  const bool gate_lds = AS && p.Cin <= kGateLds;
+  const bool gate_lds = FAST || (AS && p.Cin <= kGateLds);
+  // FAST: K groups past K (last stage, K % 32 != 0) were read from a clamped
+  // address: zeroed once the stage's MFMAs are issued (the packed weights
+  // there are zero, the pixels need not be finite)
+  auto zero_tail = [&](int s, float4 (&a)[TM][kG]) {
+    if (!FAST || (s + 1) * kBK <= Kt) return;  // wave-uniform
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+#pragma unroll
+      for (int q = 0; q < kG; ++q)
+        if (s * kBK + 8 * q + 4 * h >= Kt) a[t][q] = make_float4(0.f, 0.f, 0.f, 0.f);
+  };
   // weight stage s -> registers (ECA gate applied to the rows k < Cin when it
   // is not staged in LDS)
   auto load_b = [&](int s, float4 (&b)[NBT]) {
@@ -398,7 +448,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_m32_kernel(const ConvArgs p, i
         const int u = rem >> 6, l = rem & 63;
         const int k8 = s * kG + g;
         v = wg[((int64_t)k8 * p.Ntiles + nb * TN + u) * 64 + l];
-        if (sc && !gate_lds) {
+        if (!FAST && sc && !gate_lds) {
           int k0 = 8 * k8 + 4 * (l >> 5);
           if (KXK) k0 -= (s / cps) * p.Cin;  // channel within the stage's tap
           if (k0 < p.Cin) {
@@ -452,6 +502,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_m32_kernel(const ConvArgs p, i
     load_a(s_beg, a_cur);
     load_b(s_beg, b_nxt);
     store_b(s_beg & 1, s_beg, b_nxt);
+    zero_tail(s_beg, a_cur);
   }
   __syncthreads();
   for (int s = s_beg; s < S; ++s) {
@@ -493,6 +544,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_m32_kernel(const ConvArgs p, i
       for (int t = 0; t < TM; ++t)
 #pragma unroll
         for (int q = 0; q < kG; ++q) a_cur[t][q] = a_nxt[t][q];
+      zero_tail(s + 1, a_cur);
     }
     __syncthreads();
   }
@@ -590,6 +642,178 @@ __global__ __launch_bounds__(256) void m32_ksplit_reduce(const ConvArgs p, int k
   v.z = act32(v.z, p.act, p.slope);
   v.w = act32(v.w, p.act, p.slope);
   *reinterpret_cast<float4*>(p.y + m * p.y_ps + p.y_c0 + n) = v;
+}
+
+// 8-wave form of conv1x1_m32_kernel<1, TN> for TN >= 5 (1x1, stride 1; the
+// wide-N gated project GEMMs of MNv3, 160 channels at 32^2 / 64^2 maps).
+// With TN >= 5 a 4-wave workgroup is all a CU holds of such a layer (256
+// per-image tiles on 256 CUs), so each SIMD runs one wave and everything that
+// is not an MFMA (waits, the weight fragments' LDS reads, store_b, the stage
+// barrier) is exposed.  Same 128-pixel x 32 TN-channel tile and the same
+// double-buffered 32-channel weight stage here, on 512 threads: waves w and
+// w + 4 (one SIMD) take the same 32-pixel row; the low half the N-tiles
+// [0, (TN + 1) / 2), the high half the rest, so each SIMD has two waves to
+// switch between with the tile's MFMA work split among them.
+// The next stage's loads are issued back to back ahead of the stage's MFMAs
+// with nothing that waits on them: the pixel loads are unconditional (a row
+// past M reads the tile's first pixel, whose column is never stored; a
+// channel group past K reads a clamped address and is zeroed after the
+// MFMAs), "second source" (X2) is a compile-time choice and the gate always
+// comes from LDS (host: Cin <= kGateLds).
+// Every output element keeps conv1x1_m32_kernel's accumulation sequence
+// (stages, q, components in order) and epilogue (m32_epilogue_tm1): the same
+// bits as the 4-wave form.
+template <int TN, bool AS, bool X2>
+__global__ __launch_bounds__(512) void conv1x1_m32w8_kernel(const ConvArgs p, int mtiles_img,
+                                                            int per_img) {
+  constexpr int TNL = (TN + 1) / 2, TNH = TN - TNL;  // N-tiles of the low / high wave half
+  constexpr int NB4 = kG * TN * 64;                  // float4 of one weight stage
+  constexpr int NBT = (NB4 + 511) / 512;             // ... per thread
+  constexpr int kEpi4 = 8 * 32 * kEpiPitch / 4;      // epilogue: one slice per wave
+  constexpr int SB4 = kEpi4 > 2 * NB4 ? kEpi4 : 2 * NB4;
+  __shared__ float4 sB_[SB4];
+  float4 (*sB)[NB4] = reinterpret_cast<float4 (*)[NB4]>(sB_);
+  __shared__ __attribute__((aligned(16))) float sGate[AS ? kGateLds : 4];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int row = wave & 3, half = wave >> 2;
+  const int h = lane >> 5, j = lane & 31;
+  const int nblk_n = p.Ntiles / TN;
+  const int bid = blockIdx.x;
+  const int nb = bid % nblk_n, mb = bid / nblk_n;
+  const int OHW = p.OH * p.OW;
+  int img = 0, m_lo, m_hi;
+  if (per_img) {
+    img = mb / mtiles_img;
+    m_lo = img * OHW + (mb - img * mtiles_img) * 128;
+    m_hi = min(img * OHW + OHW, (int)p.M);
+  } else {
+    m_lo = mb * 128;
+    m_hi = (int)p.M;
+  }
+  const int m = m_lo + row * 32 + j;
+  const int pm = m < m_hi ? m : -1;
+  const int ml = pm >= 0 ? m : m_lo;  // the row this lane loads (m_lo < m_hi always)
+  const int Kt = p.Cin + (X2 ? p.Cin2 : 0);
+  const int S = (Kt + kBK - 1) / kBK;
+  const float4* wg = reinterpret_cast<const float4*>(p.w) + (int64_t)nb * TN * 64;
+  const float* xa = p.x + (int64_t)ml * p.x_ps + p.x_c0;
+  const float* xb = X2 ? p.x2 + (int64_t)ml * p.x2_ps - p.Cin : xa;
+
+  // stage s: the 4 channel groups of this lane's pixel, no branch, no wait
+  auto load_a = [&](int s, float4 (&a)[kG]) {
+#pragma unroll
+    for (int q = 0; q < kG; ++q) {
+      const int k4 = min(s * kBK + 8 * q + 4 * h, Kt - 4);  // (K % 4 == 0: the fast 1x1 layout)
+      const float* src = (X2 && k4 >= p.Cin) ? xb + k4 : xa + k4;
+      a[q] = *reinterpret_cast<const float4*>(src);
+    }
+  };
+  auto load_b = [&](int s, float4 (&b)[NBT]) {
+#pragma unroll
+    for (int i = 0; i < NBT; ++i) {
+      const int f = i * 512 + threadIdx.x;
+      if ((i + 1) * 512 <= NB4 || wave < (NB4 - i * 512) / 64) {  // wave-uniform
+        const int g = f / (TN * 64), rem = f - g * (TN * 64);
+        b[i] = wg[(int64_t)(s * kG + g) * p.Ntiles * 64 + rem];
+      }
+    }
+  };
+  auto store_b = [&](int buf, int s, const float4 (&b)[NBT]) {
+#pragma unroll
+    for (int i = 0; i < NBT; ++i) {
+      const int f = i * 512 + threadIdx.x;
+      if ((i + 1) * 512 <= NB4 || wave < (NB4 - i * 512) / 64) {
+        float4 v = b[i];
+        if constexpr (AS) {
+          const int g = f / (TN * 64), l = f & 63;
+          const int k0 = 8 * (s * kG + g) + 4 * (l >> 5);
+          if (k0 < p.Cin) {
+            const float4 s4 = *reinterpret_cast<const float4*>(sGate + k0);
+            v.x *= s4.x; v.y *= s4.y; v.z *= s4.z; v.w *= s4.w;
+          }
+        }
+        sB[buf][f] = v;
+      }
+    }
+  };
+
+  f32x16 acc[TNL];
+#pragma unroll
+  for (int u = 0; u < TNL; ++u)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[u][r] = 0.f;
+
+  float4 a_cur[kG], a_nxt[kG], b_nxt[NBT];
+  load_a(0, a_cur);
+  load_b(0, b_nxt);
+  if constexpr (AS) {
+    const float* sc = p.ascale + (int64_t)img * p.ascale_bs;
+    for (int i = threadIdx.x; i < p.Cin; i += 512) sGate[i] = sc[i];
+    __syncthreads();
+  }
+  store_b(0, 0, b_nxt);
+  // channel groups past K (the last stage of a K % 32 != 0 layer) read a
+  // clamped address: zero them (the packed weights there are zero, the pixels
+  // need not be finite)
+  auto zero_tail = [&](int s, float4 (&a)[kG]) {
+    if ((s + 1) * kBK <= Kt) return;  // wave-uniform
+#pragma unroll
+    for (int q = 0; q < kG; ++q)
+      if (s * kBK + 8 * q + 4 * h >= Kt) a[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  zero_tail(0, a_cur);
+  __syncthreads();
+  for (int s = 0; s < S; ++s) {
+    const bool more = s + 1 < S;
+    if (more) {
+      load_a(s + 1, a_nxt);
+      load_b(s + 1, b_nxt);
+    }
+    const float4* bs = sB[s & 1];
+    auto mma = [&](auto nu_, auto u0_) {
+      constexpr int NU = decltype(nu_)::value, U0 = decltype(u0_)::value;
+#pragma unroll
+      for (int q = 0; q < kG; ++q) {
+        float4 bw[NU];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) bw[u] = bs[(q * TN + U0 + u) * 64 + lane];
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+          acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(bw[u].x, a_cur[q].x, acc[u], 0, 0, 0);
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+          acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(bw[u].y, a_cur[q].y, acc[u], 0, 0, 0);
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+          acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(bw[u].z, a_cur[q].z, acc[u], 0, 0, 0);
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+          acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(bw[u].w, a_cur[q].w, acc[u], 0, 0, 0);
+      }
+    };
+    if (half == 0)
+      mma(std::integral_constant<int, TNL>{}, std::integral_constant<int, 0>{});
+    else
+      mma(std::integral_constant<int, TNH>{}, std::integral_constant<int, TNL>{});
+    if (more) {
+      store_b((s + 1) & 1, s + 1, b_nxt);
+#pragma unroll
+      for (int q = 0; q < kG; ++q) a_cur[q] = a_nxt[q];
+      zero_tail(s + 1, a_cur);
+    }
+    __syncthreads();
+  }
+
+  float* ep = reinterpret_cast<float*>(sB_) + wave * 32 * kEpiPitch;
+  if (half == 0)
+    m32_epilogue_tm1<TNL, false, false, kEpiRt>(
+        p, reinterpret_cast<const f32x16(&)[TNL]>(acc), pm, pm, 0, 0, ep, nullptr, BnEpi{}, lane,
+        nb * TN * 32);
+  else
+    m32_epilogue_tm1<TNH, false, false, kEpiRt>(
+        p, reinterpret_cast<const f32x16(&)[TNH]>(acc), pm, pm, 0, 0, ep, nullptr, BnEpi{}, lane,
+        (nb * TN + TNL) * 32);
 }
 
 // Streaming form of the 1x1 / stride-1 GEMM for short K (Cin = 32 KS, KS 2
@@ -708,6 +932,28 @@ static int64_t m32_grid(const ConvArgs& a, int TM, int TN) {
 template <int TM, int TN, bool KXK, bool AS>
 static int launch_m32_as(const ConvArgs& a, hipStream_t st);
 
+// Whether a TM = 1, TN >= 5 1x1 launch of `grid` 4-wave workgroups takes the
+// 8-wave form (conv1x1_m32w8_kernel): below two workgroups per CU a SIMD
+// would hold a single wave of the 4-wave form.  The 8-wave kernel reads the
+// gate from LDS only and a second source at stride 1 only.  JABD_M32_W8=0
+// keeps the 4-wave form (A/B).
+static bool m32_w8(const ConvArgs& a, int64_t grid) {
+  static const bool off = [] {
+    const char* e = getenv("JABD_M32_W8");
+    return e && e[0] == '0';
+  }();
+  if (off || a.tconv || (a.ascale && a.Cin > kGateLds) || (a.x2 && a.x2_stride != 1))
+    return false;
+  static int ncu = 0;
+  if (ncu <= 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      ncu = 0;
+  }
+  return grid < 2 * (int64_t)ncu;
+}
+
 template <int TM, int TN, bool KXK>
 static int launch_m32(const ConvArgs& a, hipStream_t st) {
   if (a.ascale) return launch_m32_as<TM, TN, KXK, true>(a, st);
@@ -747,6 +993,15 @@ static int launch_m32_as(const ConvArgs& a, hipStream_t st) {
     m32_ksplit_reduce<<<(unsigned)cdiv(n4, 256), 256, 0, st>>>(a, ks, part);
     return check_launch("m32_ksplit_reduce");
   }
+  if constexpr (TM == 1 && TN >= 5 && !KXK) {
+    if (m32_w8(a, grid)) {
+      if (a.x2)
+        conv1x1_m32w8_kernel<TN, AS, true><<<(unsigned)grid, 512, 0, st>>>(a, (int)mt_img, per_img);
+      else
+        conv1x1_m32w8_kernel<TN, AS, false><<<(unsigned)grid, 512, 0, st>>>(a, (int)mt_img, per_img);
+      return check_launch("conv1x1_m32", 100 * TM + TN);
+    }
+  }
   if constexpr (TM == 1 && !AS) {  // the epilogue terms specialised (m32_epilogue_tm1)
     if (!a.bias && a.act == ACT_NONE) {
       if (a.res)
@@ -754,6 +1009,17 @@ static int launch_m32_as(const ConvArgs& a, hipStream_t st) {
             <<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1, 1, nullptr, BnEpi{});
       else
         conv1x1_m32_kernel<1, TN, KXK, false, false, false, kEpiNone>
+            <<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1, 1, nullptr, BnEpi{});
+      return check_launch("conv1x1_m32", 100 * TM + TN);
+    }
+  }
+  if constexpr (AS && !KXK) {  // gate in LDS, second source at stride 1: the kSrcOne / kSrcTwo loads
+    if (a.Cin <= kGateLds && (!a.x2 || a.x2_stride == 1)) {
+      if (a.x2)
+        conv1x1_m32_kernel<TM, TN, false, true, false, false, kEpiRt, kSrcTwo>
+            <<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1, 1, nullptr, BnEpi{});
+      else
+        conv1x1_m32_kernel<TM, TN, false, true, false, false, kEpiRt, kSrcOne>
             <<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1, 1, nullptr, BnEpi{});
       return check_launch("conv1x1_m32", 100 * TM + TN);
     }
