@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/jabd.h"
 
@@ -112,6 +113,23 @@ __device__ __forceinline__ float4 dw_bn_in(float4 v, const DwBnCoef& k, int act,
     z.x = hswish_f(z.x); z.y = hswish_f(z.y); z.z = hswish_f(z.z); z.w = hswish_f(z.w);
   }
   return z;
+}
+
+// Environment switches (INTEGRATION.md lists them all).  These read the
+// environment on every call; a site keeps the result in a function-local
+// `static const`, which is initialised once and thread-safely (DataParallel
+// threads enter the launchers concurrently).
+inline const char* env_text(const char* name) { return getenv(name); }
+// the value as a decimal integer; def when the variable is unset
+inline long long env_int(const char* name, long long def) {
+  const char* e = env_text(name);
+  return e ? atoll(e) : def;
+}
+// the value's first character as a digit (the 0 / 1 / 2 switches look at
+// nothing else); def when the variable is unset or starts with no digit
+inline int env_digit(const char* name, int def = -1) {
+  const char* e = env_text(name);
+  return e && e[0] >= '0' && e[0] <= '9' ? e[0] - '0' : def;
 }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -19,6 +19,7 @@
 // optional K-concatenated second source (the block's skip branch folded into
 // the same GEMM); residual add; activation; channel-offset / strided output
 // (SSH concat, head layout).
+#include <limits.h>
 #include <stdlib.h>
 
 #include <algorithm>
@@ -641,39 +642,36 @@ __global__ __launch_bounds__(256) void conv3x3_tile_kernel(const ConvArgs p, int
   }
 }
 
-// JABD_CONV3X3_TILE=0 disables the LDS-tiled 3x3 kernel, =2 keeps it for
-// forward convs only (A/B).
-static bool conv3x3_tile_on(bool tconv) {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("JABD_CONV3X3_TILE");
-    v = e && e[0] == '0' ? 0 : (e && e[0] == '2' ? 2 : 1);
-  }
-  return v == 1 || (v == 2 && !tconv);
+static size_t conv3x3_lds(const ConvArgs& a, int tm) {
+  const size_t lds_in = (size_t)(4 * tm + 2) * k3IC * (a.Cin + 4) * sizeof(float);
+  const size_t lds_epi = (size_t)4 * 16 * (16 * a.tn + 4) * sizeof(float);
+  return std::max(lds_in, lds_epi);
 }
 
-static int conv3x3_rows_per_wave() {  // JABD_CONV3X3_TM=2|4 (A/B; 4 measured 5% slower)
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("JABD_CONV3X3_TM");
-    v = e && e[0] == '4' ? 4 : 2;
-  }
-  return v;
-}
-
-static int launch_conv3x3_tile(const ConvArgs& a, hipStream_t st) {
-  const int tn = a.tn;
-  int tm = conv3x3_rows_per_wave();
+// Whether the LDS-tiled 3x3 kernel takes the layer, and with how many rows
+// per wave.  JABD_CONV3X3_TILE=0 disables it, =2 keeps it for forward convs
+// only (A/B); JABD_CONV3X3_TM=2|4 (A/B; 4 measured 5% slower).
+static bool conv3x3_tile_pick(const ConvLayer& L, int& tm) {
+  static const int on = env_digit("JABD_CONV3X3_TILE", 1);  // 0 / 2 as above, else on
+  static const int rows = env_digit("JABD_CONV3X3_TM") == 4 ? 4 : 2;
+  const ConvArgs& a = L.a;
+  if (on == 0 || (on == 2 && a.tconv)) return false;
+  if (L.is1x1 || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.nchw_in || a.x2 ||
+      a.res || !L.vec4 || !L.v4out || a.Cin > 64 || a.tn > 3 || (a.ascale && a.ascale_bs % 4))
+    return false;
+  tm = rows;
   if (tm == 4 && (int64_t)a.B * cdiv(a.OH, 16) * cdiv(a.OW, k3Cols) < 1024) tm = 2;
+  return conv3x3_lds(a, tm) <= 64 * 1024;
+}
+
+static int launch_conv3x3_tile(const ConvArgs& a, int tm, hipStream_t st) {
+  const int tn = a.tn;
   const int rows = 4 * tm;
   const int tiles_w = (int)cdiv(a.OW, k3Cols), tiles_h = (int)cdiv(a.OH, rows);
   const int tiles_img = tiles_w * tiles_h;
   const int64_t grid = (int64_t)a.B * tiles_img * (a.Ntiles / tn);
   JABD_REQUIRE(grid < (int64_t)0x7fffffff, "conv3x3: grid too large");
-  const size_t lds_in = (size_t)(rows + 2) * k3IC * (a.Cin + 4) * sizeof(float);
-  const size_t lds_epi = (size_t)4 * 16 * (16 * tn + 4) * sizeof(float);
-  const size_t lds = std::max(lds_in, lds_epi);
-  if (lds > 64 * 1024) return -1;
+  const size_t lds = conv3x3_lds(a, tm);
 #define C3_CASE(TN_, TM_)                                                                    \
   if (tn == TN_ && tm == TM_) {                                                              \
     conv3x3_tile_kernel<TN_, TM_><<<(unsigned)grid, 256, lds, st>>>(a, tiles_w, tiles_img);  \
@@ -748,53 +746,49 @@ extern "C" int jabd_conv_pack_tn(int cout) {
 
 // JABD_CONV_GENERIC=1 forces the generic implicit-GEMM kernel (A/B tests).
 static bool conv_generic_only() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("JABD_CONV_GENERIC");
-    v = e && e[0] == '1' ? 1 : 0;
-  }
-  return v == 1;
+  static const bool v = env_digit("JABD_CONV_GENERIC") == 1;
+  return v;
 }
 
 namespace jabd {
 bool stem7_ok(const ConvArgs& a);
 int stem7_fwd_launch(const ConvArgs& a, hipStream_t st);
-int conv1x1_m32_dispatch(const ConvArgs& a, hipStream_t st, bool kxk);
-int64_t conv_m32_workspace_bytes(const ConvArgs& a, bool kxk);
-int conv_m32_stats_dispatch(const ConvArgs& a, bool kxk, float* part, const BnEpi& bb,
+bool m32s_pick(const ConvLayer& L, int form, int& TN, int& KS);
+bool m32_tile_pick(const ConvLayer& L, int& tm, int& tn, int& ks);
+int conv_m32s_launch(const ConvLayer& L, const ConvRoute& r, hipStream_t st);
+int conv_m32_tile_launch(const ConvLayer& L, const ConvRoute& r, hipStream_t st);
+int64_t conv_m32_ksplit_bytes(const ConvArgs& a, int ks);
+int conv_m32_stats_dispatch(const ConvLayer& L, bool kxk, float* part, const BnEpi& bb,
                             hipStream_t st);
 int64_t bn_rows_sum_doubles(int64_t M, int C);
 int64_t bn_rows_chunk_doubles(int64_t M, int C);
 int bn_rows_final_launch(const float* rows, int ldc, int64_t M, int C, double* chunks,
                          float* mean, float* invstd, float* rmean, float* rvar, float momentum,
                          float eps, hipStream_t st);
+bool conv1x1_stream_serves(const ConvArgs& a, bool stats);
 int conv1x1_stream_dispatch(const ConvArgs& a, hipStream_t st, StreamStats* ss = nullptr);
 }
 
-// Which 1x1 kernel: the 32x32x2 LDS-weight kernel (conv32.hip) pays off when
-// the GEMM is compute-heavy.  JABD_CONV32=0 / 1 forces it off / on (A/B).
-static bool use_conv32(const ConvArgs& a) {
-  static int v = -2;
-  if (v == -2) {
-    const char* e = getenv("JABD_CONV32");
-    v = e && e[0] == '0' ? 0 : (e && e[0] == '1' ? 1 : -1);
-  }
-  if (!a.w32 || a.tn32 <= 0 || a.ntiles32 % a.tn32 || a.ntiles32 * 32 < a.Cout) return false;
-  if (v >= 0) return v == 1;
+// Which kernel: the 32x32x2 LDS-weight kernels (conv32.hip) pay off when the
+// GEMM is compute-heavy.  JABD_CONV32=0 / 1 forces them off / on (A/B).
+static bool use_conv32(const ConvLayer& L) {
+  static const int v = env_digit("JABD_CONV32");  // 0 / 1, else the heuristic
+  const ConvArgs& a = L.a;
+  if (!L.w32(1, INT_MAX)) return false;
+  if (v == 0 || v == 1) return v == 1;
   // K 64 / 128 1x1s into >= 64 channels: the 32x32 kernel's streaming form
   // (conv1x1_m32s_kernel; R50 l1.c3-shaped GEMM 2190 -> 2005 us vs conv.hip)
-  if (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && !a.x2 && !a.ascale && !a.y2 &&
-      !a.tconv && (a.Cin == 64 || a.Cin == 128) && a.Cout >= 64)
+  if (L.is1x1 && !a.x2 && !a.ascale && !a.y2 && !a.tconv && (a.Cin == 64 || a.Cin == 128) &&
+      a.Cout >= 64)
     return true;
-  const int K = a.KH * a.KW * a.Cin + (a.x2 ? a.Cin2 : 0);
-  if (a.KH * a.KW > 1) return a.Cout >= 64 && K >= 288;
-  return a.Cout >= 96 && K >= 96;
+  if (a.KH * a.KW > 1) return a.Cout >= 64 && L.Ktot >= 288;
+  return a.Cout >= 96 && L.Ktot >= 96;
 }
 
-// Argument checks shared by the conv entry points; fills a (M, flags) and
-// reports whether the fast 1x1 kernels take the layout.
-static int conv_setup(const jabd_conv_args* args, ConvArgs& a, bool& fast1x1, bool& vec4) {
+// Argument checks shared by the conv entry points; classifies the call.
+static int conv_setup(const jabd_conv_args* args, ConvLayer& L) {
   JABD_REQUIRE(args, "conv: null args");
+  ConvArgs& a = L.a;
   a = *args;
   JABD_REQUIRE(a.x && a.w && a.y, "conv: null pointer");
   JABD_REQUIRE(a.B > 0 && a.Cin > 0 && a.Cout > 0 && a.KH > 0 && a.KW > 0 && a.stride > 0,
@@ -808,7 +802,7 @@ static int conv_setup(const jabd_conv_args* args, ConvArgs& a, bool& fast1x1, bo
                      a.OW == (a.W + 2 * a.pad - a.KW) / a.stride + 1,
                  "conv: output size mismatch");
   }
-  const bool is1x1 = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
+  L.is1x1 = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
   JABD_REQUIRE(!a.y2 || (a.nsplit > 0 && a.nsplit % 4 == 0 && a.nsplit < a.Cout &&
                          a.y2_ps % 4 == 0 && a.y2_c0 % 4 == 0 && a.y2_bs % 4 == 0 &&
                          (reinterpret_cast<uintptr_t>(a.y2) & 15) == 0 && !a.res && !a.tconv),
@@ -816,9 +810,8 @@ static int conv_setup(const jabd_conv_args* args, ConvArgs& a, bool& fast1x1, bo
   JABD_REQUIRE(!a.x2 || ((a.KH * a.KW * a.Cin) % 4 == 0 && a.Cin2 % 4 == 0 && a.x2_ps % 4 == 0 &&
                          a.x2_stride > 0 && !a.nchw_in),
                "conv: K-concat needs K and Cin2 multiples of 4");
-  (void)is1x1;
-  const int Ktot = a.KH * a.KW * a.Cin + (a.x2 ? a.Cin2 : 0);
-  JABD_REQUIRE(a.Kc == (Ktot + 15) / 16, "conv: Kc=%d, expected %d", a.Kc, (Ktot + 15) / 16);
+  L.Ktot = a.KH * a.KW * a.Cin + (a.x2 ? a.Cin2 : 0);
+  JABD_REQUIRE(a.Kc == (L.Ktot + 15) / 16, "conv: Kc=%d, expected %d", a.Kc, (L.Ktot + 15) / 16);
   const int tiles = (a.Cout + 15) / 16;
   JABD_REQUIRE(a.Ntiles >= tiles, "conv: Ntiles=%d < %d", a.Ntiles, tiles);
   a.M = (int64_t)a.B * a.OH * a.OW;
@@ -826,23 +819,23 @@ static int conv_setup(const jabd_conv_args* args, ConvArgs& a, bool& fast1x1, bo
   {
     const uintptr_t al = reinterpret_cast<uintptr_t>(a.y) | reinterpret_cast<uintptr_t>(a.bias) |
                          reinterpret_cast<uintptr_t>(a.res);
-    const bool v4 = a.Cout % 4 == 0 && a.y_ps % 4 == 0 && a.y_c0 % 4 == 0 && a.y_bs % 4 == 0 &&
-                    (!a.res || (a.res_ps % 4 == 0 && a.res_c0 % 4 == 0 && a.res_bs % 4 == 0)) &&
-                    (al & 15) == 0;
-    a.flags = v4 ? 1 : 0;
-    JABD_REQUIRE(!a.y2 || v4, "conv: split output needs the vector epilogue layout");
+    L.v4out = a.Cout % 4 == 0 && a.y_ps % 4 == 0 && a.y_c0 % 4 == 0 && a.y_bs % 4 == 0 &&
+              (!a.res || (a.res_ps % 4 == 0 && a.res_c0 % 4 == 0 && a.res_bs % 4 == 0)) &&
+              (al & 15) == 0;
+    a.flags = L.v4out ? 1 : 0;
+    JABD_REQUIRE(!a.y2 || L.v4out, "conv: split output needs the vector epilogue layout");
   }
-  vec4 = !a.nchw_in && a.Cin % 4 == 0 && a.x_ps % 4 == 0 && a.x_c0 % 4 == 0 &&
-         (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
+  L.vec4 = !a.nchw_in && a.Cin % 4 == 0 && a.x_ps % 4 == 0 && a.x_c0 % 4 == 0 &&
+           (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
   JABD_REQUIRE(a.tn > 0 && a.Ntiles % a.tn == 0, "conv: Ntiles %% tn != 0");
-  const int64_t OHW = (int64_t)a.OH * a.OW;
+  const int64_t OHW = L.OHW = (int64_t)a.OH * a.OW;
+  L.rows_contig = a.y_bs == OHW * a.y_ps && (!a.res || a.res_bs == OHW * a.res_ps);
   const int64_t maxps = std::max<int64_t>(std::max<int64_t>(a.x_ps, a.y_ps),
                                           std::max<int64_t>(a.res ? a.res_ps : 0,
                                                             a.x2 ? a.x2_ps : 0));
-  fast1x1 =
-      is1x1 && !a.tconv && vec4 && (a.flags & 1) && !a.y2 && a.x_bs == OHW * a.x_ps &&
-      a.y_bs == OHW * a.y_ps && (!a.res || a.res_bs == OHW * a.res_ps) &&
-      (!a.ascale || a.ascale_bs % 4 == 0) &&
+  L.fast1x1 =
+      L.is1x1 && !a.tconv && L.vec4 && L.v4out && !a.y2 && a.x_bs == OHW * a.x_ps &&
+      L.rows_contig && (!a.ascale || a.ascale_bs % 4 == 0) &&
       (!a.x2 || (a.x2_stride == 1 ? (a.x2_W == a.OW && a.x2_bs == OHW * a.x2_ps)
                                   : (a.x2_stride > 1 && a.x2_bs % a.x2_ps == 0 &&
                                      a.x2_bs * a.B < ((int64_t)1 << 31)))) &&
@@ -850,150 +843,203 @@ static int conv_setup(const jabd_conv_args* args, ConvArgs& a, bool& fast1x1, bo
   return 0;
 }
 
-// Whether jabd_conv2d_nhwc_f32 hands the layer to the 32x32 tile GEMM
-// (conv1x1_m32_dispatch): 0 no, 1 its 1x1 form, 2 its k x k implicit GEMM
-// (32-channel stages inside one tap).  jabd_conv_workspace_size asks the same
-// question, so a split-K workspace is sized for exactly the layers that split.
-static int conv_m32_route(const ConvArgs& a, bool fast1x1, bool vec4) {
-  const bool is1x1 = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
-  const int64_t OHW = (int64_t)a.OH * a.OW;
-  if (is1x1) return fast1x1 && use_conv32(a) ? 1 : 0;
-  const bool kxk = vec4 && (a.flags & 1) && !a.x2 && !a.y2 && a.Cin % 32 == 0 &&
-                   (!a.tconv || a.stride == 1 || (a.stride == 2 && !a.ascale)) &&
-                   a.x_bs % 4 == 0 && a.y_bs == OHW * a.y_ps &&
-                   (!a.res || a.res_bs == OHW * a.res_ps) && use_conv32(a);
-  return kxk ? 2 : 0;
+// The generic kernels' pixel tiles per wave: 4 x 16 by default; small-M layers
+// (the SSH / FPN convs at 32x32 and 64x64) drop to 2 or 1 so the grid still
+// fills the 256 CUs several times over.
+static int conv_generic_tm(const ConvLayer& L) {
+  const ConvArgs& a = L.a;
+  const int tn = a.tn;
+  const int64_t nblk_n = a.Ntiles / tn;
+  auto grid_for = [&](int tm) { return cdiv(a.M, (int64_t)64 * tm) * nblk_n; };
+  // Short-K GEMMs are load-latency bound with few k-steps per wave: fewer
+  // pixel tiles per wave (fewer VGPRs, more resident waves) overlap more
+  // loads with MFMAs (measured on the C2 layers: tools/convbench.py).
+  const int K = L.Ktot;
+  const int tm_max = tn == 8 ? 2 : (K <= 32 ? 2 : (K <= 160 ? 1 : (K <= 400 ? 2 : 4)));
+  int tm = tm_max;
+  while (tm > 1 && grid_for(tm) < 1024) tm >>= 1;
+  // JABD_CONV_TM=1|2|4 forces the pixel tiles per wave (A/B experiments)
+  static const int ftm = (int)env_int("JABD_CONV_TM", 0);
+  if (ftm == 1 || ftm == 2 || (ftm == 4 && tn != 8)) tm = ftm;
+  return tm;
+}
+
+// The one place that decides which kernel family a forward call goes to:
+// jabd_conv2d_nhwc_f32 switches on it, jabd_conv_workspace_size and
+// conv_stats_form read it.  Each family's own conditions live next to its
+// launcher (*_pick / *_serves); here is only the order they are asked in and
+// the throughput heuristic (use_conv32) between the 32x32 and 16x16 kernels.
+static ConvRoute conv_route(const ConvLayer& L) {
+  const ConvArgs& a = L.a;
+  ConvRoute r{kFamGemm, 0, a.tn, 1};
+  // ResNet-50 7x7/s2 stem over the NCHW input (stem7.hip); JABD_STEM7=0 -> generic
+  static const bool stem7_on = env_digit("JABD_STEM7") != 0;
+  if (stem7_on && stem7_ok(a) && L.v4out && (a.act == ACT_NONE || a.act == ACT_RELU) &&
+      a.Ntiles >= 4 && !conv_generic_only()) {
+    r.family = kFamStem7;
+    return r;
+  }
+  if (use_conv32(L)) {
+    if (L.fast1x1 && m32s_pick(L, 0, r.tn, r.ks)) {
+      r.family = kFamM32Stream;
+      return r;
+    }
+    if (m32_tile_pick(L, r.tm, r.tn, r.ks)) {
+      r.family = L.is1x1 ? kFamM32Tile : kFamM32Kxk;
+      return r;
+    }
+    r = ConvRoute{kFamGemm, 0, a.tn, 1};
+  }
+  // short-K / narrow-N 1x1: the streaming kernel (conv_stream.hip)
+  if (L.fast1x1 && !a.reserved1 && conv1x1_stream_serves(a, false)) {
+    r.family = kFamStream;
+    return r;
+  }
+  if (conv3x3_tile_pick(L, r.tm)) {
+    r.family = kFamTile3x3;
+    return r;
+  }
+  r.tm = conv_generic_tm(L);
+  r.family = L.fast1x1 ? kFamConv1x1 : kFamGemm;
+  return r;
 }
 
 extern "C" int64_t jabd_conv_workspace_size(const jabd_conv_args* args) {
-  ConvArgs a;
-  bool fast1x1 = false, vec4 = false;
-  if (!args || conv_setup(args, a, fast1x1, vec4) != JABD_OK) return 0;
-  const int route = conv_m32_route(a, fast1x1, vec4);
-  return route ? conv_m32_workspace_bytes(a, route == 2) : 0;
+  ConvLayer L;
+  if (!args || conv_setup(args, L) != JABD_OK) return 0;
+  const ConvRoute r = conv_route(L);
+  const bool tile = r.family == kFamM32Tile || r.family == kFamM32Kxk;
+  return tile ? conv_m32_ksplit_bytes(L.a, r.ks) : 0;
 }
 
 // The statistics form of the streaming 1x1 conv serves the layer iff the
-// plain entry point would route it to the streaming kernel and it carries no
-// gate, second source or residual.
-static bool conv_stats_form(const ConvArgs& a, bool fast1x1) {
-  return fast1x1 && !use_conv32(a) && !a.reserved1 && !a.ascale && !a.x2 && !a.res;
+// plain entry point routes it to the streaming kernel, it carries no gate,
+// second source or residual, and the kernel has the statistics instance.
+static bool conv_stats_form(const ConvLayer& L) {
+  const ConvArgs& a = L.a;
+  return !a.ascale && !a.x2 && !a.res && conv_route(L).family == kFamStream &&
+         conv1x1_stream_serves(a, true);
 }
 
 extern "C" int64_t jabd_conv1x1_bn_stats_nblk(const jabd_conv_args* args) {
-  ConvArgs a;
-  bool fast1x1 = false, vec4 = false;
-  if (conv_setup(args, a, fast1x1, vec4) != JABD_OK || !conv_stats_form(a, fast1x1)) return 0;
+  ConvLayer L;
+  if (conv_setup(args, L) != JABD_OK || !conv_stats_form(L)) return 0;
   jabd::StreamStats ss{nullptr, nullptr, 0, true};
-  if (jabd::conv1x1_stream_dispatch(a, nullptr, &ss) != 0) return 0;
+  if (jabd::conv1x1_stream_dispatch(L.a, nullptr, &ss) != 0) return 0;
   return ss.nblk;
 }
 
 extern "C" int jabd_conv1x1_bn_stats_f32(const jabd_conv_args* args, float* part, int64_t nblk,
                                          float* shift, jabd_stream_t stream) {
-  ConvArgs a;
-  bool fast1x1 = false, vec4 = false;
-  const int e = conv_setup(args, a, fast1x1, vec4);
-  if (e != JABD_OK) return e;
-  JABD_REQUIRE(conv_stats_form(a, fast1x1),
+  ConvLayer L;
+  if (const int e = conv_setup(args, L)) return e;
+  JABD_REQUIRE(conv_stats_form(L),
                "conv1x1_bn_stats: layer not served by the streaming statistics form");
   jabd::StreamStats ss{part, shift, nblk, false};
-  const int r = jabd::conv1x1_stream_dispatch(a, as_stream(stream), &ss);
+  const int r = jabd::conv1x1_stream_dispatch(L.a, as_stream(stream), &ss);
   JABD_REQUIRE(r >= 0, "conv1x1_bn_stats: no streaming kernel for this shape");
   return r;
 }
 
-// The 32x32 GEMM's statistics form (conv32.hip, ST): a bias-free,
-// activation-free forward conv with no gate, residual, second source or
-// split output whose BatchNorm follows — the ResNet-50 bottleneck convs
-// (nets/resnet_pytorch_r.py:122-143).  The GEMM takes the shape even where
+// What the 32x32 GEMM's statistics (ST) and BatchNorm-backward (BB) forms
+// share: a bias-free, activation-free conv with no gate, second source or
+// split output, a float4 epilogue and tn32 <= 4; 1x1 in the fast-1x1 layout,
+// k x k in the 32x32 kernel's.  The GEMM takes the shape even where
 // use_conv32's throughput heuristic would pick another kernel (the saved
-// statistics pass outweighs it); JABD_CONV_STATS32=0 turns the form off.
-static bool conv_m32_stats_form(const ConvArgs& a, bool fast1x1, bool vec4, bool& kxk) {
-  static const bool on = [] {
-    const char* e = getenv("JABD_CONV_STATS32");
-    return !(e && e[0] == '0');
-  }();
-  const bool is1x1 = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
-  kxk = !is1x1;
-  const int64_t OHW = (int64_t)a.OH * a.OW;
-  if (!on || conv_generic_only() || a.bias || a.res || a.ascale || a.x2 || a.y2 ||
-      a.act != ACT_NONE || a.tconv || a.nchw_in || !(a.flags & 1) || a.Cout % 4)
+// pass outweighs it).  kxk: whether the k x k kernel serves it.
+static bool conv_m32_epi_form(const ConvLayer& L, bool kxk) {
+  const ConvArgs& a = L.a;
+  if (conv_generic_only() || a.bias || a.ascale || a.x2 || a.y2 || a.act != ACT_NONE ||
+      a.nchw_in || !L.v4out || !L.w32(1, 4))
     return false;
-  if (!a.w32 || a.tn32 < 1 || a.tn32 > 4 || a.ntiles32 % a.tn32 || a.ntiles32 * 32 < a.Cout)
-    return false;
-  if (is1x1) return fast1x1;
-  return vec4 && a.Cin % 32 == 0 && a.x_bs % 4 == 0 && a.y_bs == OHW * a.y_ps;
+  return kxk ? L.kxk32() : L.fast1x1;
 }
 
-// floats of the statistics rows (ceil(M / 32) x 2 x ntiles32 * 32) followed
-// by the fp64 chunk sums (8-byte aligned)
+// The statistics form (conv32.hip, ST): a forward conv with no residual
+// whose BatchNorm follows — the ResNet-50 bottleneck convs
+// (nets/resnet_pytorch_r.py:122-143).  JABD_CONV_STATS32=0 turns it off.
+static bool conv_m32_stats_form(const ConvLayer& L, bool& kxk) {
+  static const bool on = env_digit("JABD_CONV_STATS32") != 0;
+  kxk = !L.is1x1;
+  return on && !L.a.res && !L.a.tconv && L.a.Cout % 4 == 0 && conv_m32_epi_form(L, kxk);
+}
+
+// floats of the statistics rows (ceil(M / 32) x 2 x ntiles32 * 32), rounded
+// to the 8-byte alignment of the fp64 chunk sums that follow them
 static int64_t conv_stats_rows_floats(const ConvArgs& a) {
-  return cdiv(a.M, (int64_t)32) * 2 * a.ntiles32 * 32;
+  return (cdiv(a.M, (int64_t)32) * 2 * a.ntiles32 * 32 + 1) & ~(int64_t)1;
+}
+static int64_t conv_stats_part_floats(const ConvArgs& a) {
+  return conv_stats_rows_floats(a) + 2 * bn_rows_chunk_doubles(a.M, a.Cout);
 }
 
 extern "C" int64_t jabd_conv_bn_stats_part_floats(const jabd_conv_args* args) {
-  ConvArgs a;
-  bool fast1x1 = false, vec4 = false, kxk = false;
-  if (conv_setup(args, a, fast1x1, vec4) != JABD_OK || !conv_m32_stats_form(a, fast1x1, vec4, kxk))
-    return 0;
-  const int64_t rows = (conv_stats_rows_floats(a) + 1) & ~(int64_t)1;
-  return rows + 2 * bn_rows_chunk_doubles(a.M, a.Cout);
+  ConvLayer L;
+  bool kxk = false;
+  if (conv_setup(args, L) != JABD_OK || !conv_m32_stats_form(L, kxk)) return 0;
+  return conv_stats_part_floats(L.a);
 }
 
 extern "C" int jabd_conv_bn_stats_f32(const jabd_conv_args* args, float* part, int64_t part_floats,
                                       float* mean, float* invstd, float* running_mean,
                                       float* running_var, float momentum, float eps,
                                       jabd_stream_t stream) {
-  ConvArgs a;
-  bool fast1x1 = false, vec4 = false, kxk = false;
-  {
-    const int e = conv_setup(args, a, fast1x1, vec4);
-    if (e != JABD_OK) return e;
-  }
-  JABD_REQUIRE(conv_m32_stats_form(a, fast1x1, vec4, kxk),
+  ConvLayer L;
+  bool kxk = false;
+  if (const int e = conv_setup(args, L)) return e;
+  const ConvArgs& a = L.a;
+  JABD_REQUIRE(conv_m32_stats_form(L, kxk),
                "conv_bn_stats: layer not served by the 32x32 statistics form");
-  const int64_t rows = (conv_stats_rows_floats(a) + 1) & ~(int64_t)1;
-  JABD_REQUIRE(part && mean && invstd && part_floats >= rows + 2 * bn_rows_chunk_doubles(a.M, a.Cout),
+  JABD_REQUIRE(part && mean && invstd && part_floats >= conv_stats_part_floats(a),
                "conv_bn_stats: part holds %lld floats, %lld needed", (long long)part_floats,
-               (long long)(rows + 2 * bn_rows_chunk_doubles(a.M, a.Cout)));
+               (long long)conv_stats_part_floats(a));
   JABD_REQUIRE(((uintptr_t)part & 15) == 0, "conv_bn_stats: part must be 16-byte aligned");
   hipStream_t st = as_stream(stream);
-  const int r = conv_m32_stats_dispatch(a, kxk, part, BnEpi{}, st);
+  const int r = conv_m32_stats_dispatch(L, kxk, part, BnEpi{}, st);
   if (r != JABD_OK) return r < 0 ? JABD_EINVAL : r;
   return bn_rows_final_launch(part, a.ntiles32 * 32, a.M, a.Cout,
-                              reinterpret_cast<double*>(part + rows), mean, invstd, running_mean,
-                              running_var, momentum, eps, st);
+                              reinterpret_cast<double*>(part + conv_stats_rows_floats(a)), mean,
+                              invstd, running_mean, running_var, momentum, eps, st);
 }
 
-// The BatchNorm-backward form (BB): a bias-free data gradient (1x1 plain,
-// or k x k transposed at stride 1) whose output is the dy of a BatchNorm +
-// ReLU / LeakyReLU / identity with Cout % 32 == 0 (the R50 bottleneck's bn1 /
-// bn2 backward, nets/resnet_pytorch_r.py:122-143).
-static bool conv_m32_bb_form(const ConvArgs& a, bool fast1x1, bool vec4, bool& kxk) {
-  static const bool on = [] {
-    const char* e = getenv("JABD_CONV_BNBWD32");
-    return !(e && e[0] == '0');
-  }();
-  const bool is1x1 = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && !a.tconv;
-  kxk = !is1x1;
-  const int64_t OHW = (int64_t)a.OH * a.OW;
-  if (!on || conv_generic_only() || a.bias || a.res || a.ascale || a.x2 || a.y2 ||
-      a.act != ACT_NONE || a.nchw_in || !(a.flags & 1) || a.Cout % 32)
+// The BatchNorm-backward form (BB): a data gradient (1x1 plain, or k x k
+// transposed at stride 1) whose output is the dy of a BatchNorm + ReLU /
+// LeakyReLU / identity with Cout % 32 == 0 and no padded N tile (the R50
+// bottleneck's bn1 / bn2 backward, nets/resnet_pytorch_r.py:122-143).  A 1x1
+// data gradient given as a transposed conv runs on the k x k kernel.
+// with_res: the residual-ReLU entry point's 1x1-only variant.
+static bool conv_m32_bb_form(const ConvLayer& L, bool with_res, bool& kxk) {
+  static const bool on = env_digit("JABD_CONV_BNBWD32") != 0;
+  const ConvArgs& a = L.a;
+  kxk = !(L.is1x1 && !a.tconv);
+  if (!on || (with_res ? kxk : a.res != nullptr) || a.Cout % 32 || a.ntiles32 * 32 != a.Cout ||
+      (a.tconv && a.stride != 1))
     return false;
-  if (!a.w32 || a.tn32 < 1 || a.tn32 > 4 || a.ntiles32 % a.tn32 || a.ntiles32 * 32 != a.Cout)
-    return false;
-  if (is1x1) return fast1x1;
-  return vec4 && a.Cin % 32 == 0 && a.x_bs % 4 == 0 && a.y_bs == OHW * a.y_ps &&
-         (!a.tconv || a.stride == 1);
+  return conv_m32_epi_form(L, kxk);
+}
+
+static int64_t conv_bb_part_floats(const ConvArgs& a) {
+  return cdiv(a.M, (int64_t)32) * 2 * a.Cout + 2 * bn_rows_sum_doubles(a.M, a.Cout);
+}
+
+// The form and workspace checks of the two BatchNorm-backward entry points.
+static int conv_bb_check(const ConvLayer& L, bool with_res, const char* who, const float* part,
+                         int64_t part_floats, bool& kxk) {
+  JABD_REQUIRE(conv_m32_bb_form(L, with_res, kxk),
+               "%s: layer not served by the 32x32 BatchNorm-backward form%s", who,
+               with_res ? " (1x1 / stride-1 only)" : "");
+  const int64_t need = conv_bb_part_floats(L.a);
+  JABD_REQUIRE(part && part_floats >= need && ((uintptr_t)part & 15) == 0,
+               "%s: part holds %lld floats, %lld needed (16-byte aligned)", who,
+               (long long)part_floats, (long long)need);
+  return JABD_OK;
 }
 
 extern "C" int64_t jabd_conv_bn_bwd_part_floats(const jabd_conv_args* args) {
-  ConvArgs a;
-  bool fast1x1 = false, vec4 = false, kxk = false;
-  if (conv_setup(args, a, fast1x1, vec4) != JABD_OK || !conv_m32_bb_form(a, fast1x1, vec4, kxk))
-    return 0;
-  return cdiv(a.M, (int64_t)32) * 2 * a.Cout + 2 * bn_rows_sum_doubles(a.M, a.Cout);
+  ConvLayer L;
+  bool kxk = false;
+  if (conv_setup(args, L) != JABD_OK || !conv_m32_bb_form(L, false, kxk)) return 0;
+  return conv_bb_part_floats(L.a);
 }
 
 extern "C" int jabd_conv_bn_bwd_sums_f32(const jabd_conv_args* args, const float* x, int32_t x_ps,
@@ -1001,23 +1047,15 @@ extern "C" int jabd_conv_bn_bwd_sums_f32(const jabd_conv_args* args, const float
                                          const float* gamma, const float* beta, int32_t act,
                                          float slope, float* part, int64_t part_floats,
                                          jabd_stream_t stream) {
-  ConvArgs a;
-  bool fast1x1 = false, vec4 = false, kxk = false;
-  {
-    const int e = conv_setup(args, a, fast1x1, vec4);
-    if (e != JABD_OK) return e;
-  }
-  JABD_REQUIRE(conv_m32_bb_form(a, fast1x1, vec4, kxk),
-               "conv_bn_bwd_sums: layer not served by the 32x32 BatchNorm-backward form");
-  JABD_REQUIRE(x && mean && invstd && gamma && beta && part && x_ps % 4 == 0 && x_ps >= a.Cout &&
+  ConvLayer L;
+  bool kxk = false;
+  if (const int e = conv_setup(args, L)) return e;
+  if (const int e = conv_bb_check(L, false, "conv_bn_bwd_sums", part, part_floats, kxk)) return e;
+  JABD_REQUIRE(x && mean && invstd && gamma && beta && x_ps % 4 == 0 && x_ps >= L.a.Cout &&
                    (act == ACT_NONE || act == ACT_RELU || act == ACT_LEAKY),
                "conv_bn_bwd_sums: bad BatchNorm arguments");
-  const int64_t need = cdiv(a.M, (int64_t)32) * 2 * a.Cout + 2 * bn_rows_sum_doubles(a.M, a.Cout);
-  JABD_REQUIRE(part_floats >= need && ((uintptr_t)part & 15) == 0,
-               "conv_bn_bwd_sums: part holds %lld floats, %lld needed (16-byte aligned)",
-               (long long)part_floats, (long long)need);
   BnEpi bb{x, mean, invstd, gamma, beta, part, x_ps, act, slope};
-  const int r = conv_m32_stats_dispatch(a, kxk, nullptr, bb, as_stream(stream));
+  const int r = conv_m32_stats_dispatch(L, kxk, nullptr, bb, as_stream(stream));
   return r < 0 ? JABD_EINVAL : r;
 }
 
@@ -1031,94 +1069,44 @@ extern "C" int jabd_conv_bn_bwd_sums_res_f32(const jabd_conv_args* args, const f
                                              int32_t x_ps, const float* mask, int32_t mask_ps,
                                              const float* mean, const float* invstd, float* part,
                                              int64_t part_floats, jabd_stream_t stream) {
-  ConvArgs a;
-  bool fast1x1 = false, vec4 = false, kxk = false;
-  {
-    const int e = conv_setup(args, a, fast1x1, vec4);
-    if (e != JABD_OK) return e;
-  }
-  ConvArgs ab = a;  // the form check without the residual
-  ab.res = nullptr;
-  JABD_REQUIRE(conv_m32_bb_form(ab, fast1x1, vec4, kxk) && !kxk,
-               "conv_bn_bwd_sums_res: layer not served (1x1 / stride-1 32x32 form only)");
-  JABD_REQUIRE(!a.res || (a.res_ps % 4 == 0 && a.res_c0 % 4 == 0),
-               "conv_bn_bwd_sums_res: residual rows must be float4-aligned");
-  JABD_REQUIRE(x && mask && mean && invstd && part && x_ps % 4 == 0 && x_ps >= a.Cout &&
-                   mask_ps % 4 == 0 && mask_ps >= a.Cout,
+  ConvLayer L;
+  bool kxk = false;
+  if (const int e = conv_setup(args, L)) return e;
+  if (const int e = conv_bb_check(L, true, "conv_bn_bwd_sums_res", part, part_floats, kxk))
+    return e;
+  JABD_REQUIRE(x && mask && mean && invstd && x_ps % 4 == 0 && x_ps >= L.a.Cout &&
+                   mask_ps % 4 == 0 && mask_ps >= L.a.Cout,
                "conv_bn_bwd_sums_res: bad BatchNorm arguments");
-  const int64_t need = cdiv(a.M, (int64_t)32) * 2 * a.Cout + 2 * bn_rows_sum_doubles(a.M, a.Cout);
-  JABD_REQUIRE(part_floats >= need && ((uintptr_t)part & 15) == 0,
-               "conv_bn_bwd_sums_res: part holds %lld floats, %lld needed (16-byte aligned)",
-               (long long)part_floats, (long long)need);
   BnEpi bb{x, mean, invstd, nullptr, nullptr, part, x_ps, ACT_NONE, 0.f, mask, mask_ps};
-  const int r = conv_m32_stats_dispatch(a, false, nullptr, bb, as_stream(stream));
+  const int r = conv_m32_stats_dispatch(L, false, nullptr, bb, as_stream(stream));
   return r < 0 ? JABD_EINVAL : r;
 }
 
 extern "C" int jabd_conv2d_nhwc_f32(const jabd_conv_args* args, jabd_stream_t stream) {
-  ConvArgs a;
-  bool fast1x1 = false, vec4 = false;
-  {
-    const int e = conv_setup(args, a, fast1x1, vec4);
-    if (e != JABD_OK) return e;
-  }
-  const bool is1x1 = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
+  ConvLayer L;
+  if (const int e = conv_setup(args, L)) return e;
+  const ConvArgs& a = L.a;
   hipStream_t st = as_stream(stream);
-  const int tn = a.tn;
-  const int64_t OHW = (int64_t)a.OH * a.OW;
-  // ResNet-50 7x7/s2 stem over the NCHW input (stem7.hip); JABD_STEM7=0 -> generic
-  static const bool stem7_on = [] {
-    const char* e = getenv("JABD_STEM7");
-    return !(e && e[0] == '0');
-  }();
-  if (stem7_on && stem7_ok(a) && (a.flags & 1) && (a.act == ACT_NONE || a.act == ACT_RELU) &&
-      a.Ntiles >= 4 && !conv_generic_only())
-    return stem7_fwd_launch(a, st);
-  const int m32 = conv_m32_route(a, fast1x1, vec4);
-  if (m32 == 1) {
-    const int r = conv1x1_m32_dispatch(a, st, false);
-    if (r >= 0) return r;
+  ConvRoute r = conv_route(L);
+  int e = -1;
+  switch (r.family) {
+    case kFamStem7: return stem7_fwd_launch(a, st);
+    case kFamM32Stream: e = conv_m32s_launch(L, r, st); break;
+    case kFamM32Tile:
+    case kFamM32Kxk: e = conv_m32_tile_launch(L, r, st); break;
+    case kFamStream: e = conv1x1_stream_dispatch(a, st); break;
+    case kFamTile3x3: e = launch_conv3x3_tile(a, r.tm, st); break;
+    case kFamConv1x1:
+    case kFamGemm: break;
   }
-  if (fast1x1 && !a.reserved1) {  // short-K / narrow-N: streaming kernel (conv_stream.hip)
-    const int r = conv1x1_stream_dispatch(a, st);
-    if (r >= 0) return r;
-  }
-  // k x k implicit GEMM on the 32x32 kernel: 32-channel stages inside one tap
-  if (m32 == 2) {
-    const int r = conv1x1_m32_dispatch(a, st, true);
-    if (r >= 0) return r;
-  }
-  if (!is1x1 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && !a.nchw_in &&
-      !a.x2 && !a.res && vec4 && (a.flags & 1) && a.Cin <= 64 && a.tn <= 3 &&
-      (!a.ascale || a.ascale_bs % 4 == 0) && conv3x3_tile_on(a.tconv)) {
-    const int r = launch_conv3x3_tile(a, st);
-    if (r >= 0) return r;
-  }
-  // Pixel tiles per wave: 4 x 16 by default; small-M layers (the SSH / FPN
-  // convs at 32x32 and 64x64) drop to 2 or 1 so the grid still fills the
-  // 256 CUs several times over.
-  const int64_t nblk_n = a.Ntiles / tn;
-  auto grid_for = [&](int tm) { return cdiv(a.M, (int64_t)64 * tm) * nblk_n; };
-  // Short-K GEMMs are load-latency bound with few k-steps per wave: fewer
-  // pixel tiles per wave (fewer VGPRs, more resident waves) overlap more
-  // loads with MFMAs (measured on the C2 layers: tools/convbench.py).
-  const int Kall = a.KH * a.KW * a.Cin + (a.x2 ? a.Cin2 : 0);
-  const int tm_max = tn == 8 ? 2 : (Kall <= 32 ? 2 : (Kall <= 160 ? 1 : (Kall <= 400 ? 2 : 4)));
-  int tm = tm_max;
-  while (tm > 1 && grid_for(tm) < 1024) tm >>= 1;
-  {  // JABD_CONV_TM=1|2|4 forces the pixel tiles per wave (A/B experiments)
-    static int ftm = -1;
-    if (ftm < 0) {
-      const char* e = getenv("JABD_CONV_TM");
-      ftm = e ? atoi(e) : 0;
-    }
-    if (ftm == 1 || ftm == 2 || (ftm == 4 && tn != 8)) tm = ftm;
-  }
-  const int r = fast1x1 ? dispatch_conv<true>(a, tn, tm, vec4, st) : -1;
-  if (r >= 0) return r;
-  const int r2 = dispatch_conv<false>(a, tn, tm, vec4, st);
-  if (r2 >= 0) return r2;
-  set_error("conv: unsupported tn=%d", tn);
+  if (e >= 0) return e;
+  // the generic kernels: a layer no family above takes, or one whose launcher
+  // met a failure only the runtime reports (the streaming kernel's occupancy)
+  if (r.family != kFamConv1x1 && r.family != kFamGemm) r.tm = conv_generic_tm(L);
+  e = L.fast1x1 ? dispatch_conv<true>(a, a.tn, r.tm, L.vec4, st) : -1;
+  if (e < 0) e = dispatch_conv<false>(a, a.tn, r.tm, L.vec4, st);
+  if (e >= 0) return e;
+  set_error("conv: unsupported tn=%d", a.tn);
   return JABD_EINVAL;
 }
 

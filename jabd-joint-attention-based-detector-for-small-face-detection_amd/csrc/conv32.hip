@@ -921,7 +921,7 @@ static int64_t m32_ksplit_bytes(const ConvArgs& a, int ks) {
 }
 // Workgroups of a plain (non-phase) launch with TM x TN wave tiles: M is tiled
 // per image under the ECA gate, flat otherwise.  The launch and the workspace
-// query (conv_m32_workspace_bytes) both take the grid from here.
+// query (through m32_tile_pick) both take the grid from here.
 static int64_t m32_grid(const ConvArgs& a, int TM, int TN) {
   const int64_t BM = 4 * 32 * TM;
   const int64_t OHW = (int64_t)a.OH * a.OW;
@@ -929,19 +929,13 @@ static int64_t m32_grid(const ConvArgs& a, int TM, int TN) {
   return mtiles * (a.ntiles32 / TN);
 }
 
-template <int TM, int TN, bool KXK, bool AS>
-static int launch_m32_as(const ConvArgs& a, hipStream_t st);
-
 // Whether a TM = 1, TN >= 5 1x1 launch of `grid` 4-wave workgroups takes the
 // 8-wave form (conv1x1_m32w8_kernel): below two workgroups per CU a SIMD
 // would hold a single wave of the 4-wave form.  The 8-wave kernel reads the
 // gate from LDS only and a second source at stride 1 only.  JABD_M32_W8=0
 // keeps the 4-wave form (A/B).
 static bool m32_w8(const ConvArgs& a, int64_t grid) {
-  static const bool off = [] {
-    const char* e = getenv("JABD_M32_W8");
-    return e && e[0] == '0';
-  }();
+  static const bool off = env_digit("JABD_M32_W8") == 0;
   if (off || a.tconv || (a.ascale && a.Cin > kGateLds) || (a.x2 && a.x2_stride != 1))
     return false;
   static int ncu = 0;
@@ -954,14 +948,9 @@ static bool m32_w8(const ConvArgs& a, int64_t grid) {
   return grid < 2 * (int64_t)ncu;
 }
 
-template <int TM, int TN, bool KXK>
-static int launch_m32(const ConvArgs& a, hipStream_t st) {
-  if (a.ascale) return launch_m32_as<TM, TN, KXK, true>(a, st);
-  return launch_m32_as<TM, TN, KXK, false>(a, st);
-}
-
+// ks: the K split m32_tile_pick chose; taken when the caller's workspace holds it
 template <int TM, int TN, bool KXK, bool AS>
-static int launch_m32_as(const ConvArgs& a, hipStream_t st) {
+static int launch_m32_as(const ConvArgs& a, int ks, hipStream_t st) {
   constexpr int BM = 4 * 32 * TM;
   const int64_t OHW = (int64_t)a.OH * a.OW;
   const int per_img = a.ascale != nullptr;
@@ -983,8 +972,7 @@ static int launch_m32_as(const ConvArgs& a, hipStream_t st) {
   }
   const int64_t grid = m32_grid(a, TM, TN);  // (a.Ntiles == a.ntiles32 here)
   JABD_REQUIRE(grid < (int64_t)0x7fffffff, "conv32: grid too large");
-  const int ks = a.ws ? m32_ksplit(a, KXK, grid) : 1;
-  if (ks > 1 && a.ws_bytes >= m32_ksplit_bytes(a, ks)) {
+  if (ks > 1 && a.ws && a.ws_bytes >= m32_ksplit_bytes(a, ks)) {
     float* part = static_cast<float*>(a.ws);
     conv1x1_m32_kernel<TM, TN, KXK, AS><<<dim3((unsigned)grid, (unsigned)ks), 256, 0, st>>>(
         a, (int)mt_img, per_img, -1, ks, part, BnEpi{});
@@ -1002,41 +990,33 @@ static int launch_m32_as(const ConvArgs& a, hipStream_t st) {
       return check_launch("conv1x1_m32", 100 * TM + TN);
     }
   }
+  // the plain launch: every instance has the default one's signature
+  auto kern = conv1x1_m32_kernel<TM, TN, KXK, AS>;
   if constexpr (TM == 1 && !AS) {  // the epilogue terms specialised (m32_epilogue_tm1)
-    if (!a.bias && a.act == ACT_NONE) {
-      if (a.res)
-        conv1x1_m32_kernel<1, TN, KXK, false, false, false, kEpiRes>
-            <<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1, 1, nullptr, BnEpi{});
-      else
-        conv1x1_m32_kernel<1, TN, KXK, false, false, false, kEpiNone>
-            <<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1, 1, nullptr, BnEpi{});
-      return check_launch("conv1x1_m32", 100 * TM + TN);
-    }
+    if (!a.bias && a.act == ACT_NONE)
+      kern = a.res ? conv1x1_m32_kernel<1, TN, KXK, false, false, false, kEpiRes>
+                   : conv1x1_m32_kernel<1, TN, KXK, false, false, false, kEpiNone>;
   }
   if constexpr (AS && !KXK) {  // gate in LDS, second source at stride 1: the kSrcOne / kSrcTwo loads
-    if (a.Cin <= kGateLds && (!a.x2 || a.x2_stride == 1)) {
-      if (a.x2)
-        conv1x1_m32_kernel<TM, TN, false, true, false, false, kEpiRt, kSrcTwo>
-            <<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1, 1, nullptr, BnEpi{});
-      else
-        conv1x1_m32_kernel<TM, TN, false, true, false, false, kEpiRt, kSrcOne>
-            <<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1, 1, nullptr, BnEpi{});
-      return check_launch("conv1x1_m32", 100 * TM + TN);
-    }
+    if (a.Cin <= kGateLds && (!a.x2 || a.x2_stride == 1))
+      kern = a.x2 ? conv1x1_m32_kernel<TM, TN, false, true, false, false, kEpiRt, kSrcTwo>
+                  : conv1x1_m32_kernel<TM, TN, false, true, false, false, kEpiRt, kSrcOne>;
   }
-  conv1x1_m32_kernel<TM, TN, KXK, AS><<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1,
-                                                                     1, nullptr, BnEpi{});
+  kern<<<(unsigned)grid, 256, 0, st>>>(a, (int)mt_img, per_img, -1, 1, nullptr, BnEpi{});
   return check_launch("conv1x1_m32", 100 * TM + TN);
+}
+
+template <int TM, int TN, bool KXK>
+static int launch_m32(const ConvArgs& a, int ks, hipStream_t st) {
+  if (a.ascale) return launch_m32_as<TM, TN, KXK, true>(a, ks, st);
+  return launch_m32_as<TM, TN, KXK, false>(a, ks, st);
 }
 
 // conv1x1_m32s_kernel launch: a persistent grid of (CUs x resident
 // workgroups) rounded to whole N blocks.  JABD_M32S=0 keeps every layer on
 // conv1x1_m32_kernel (A/B).
 static bool m32s_on() {
-  static const bool on = [] {
-    const char* e = getenv("JABD_M32S");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_digit("JABD_M32S") != 0;
   return on;
 }
 
@@ -1061,59 +1041,47 @@ static int launch_m32s(const ConvArgs& a, float* part, const BnEpi& bb, hipStrea
   return check_launch("conv1x1_m32s", 100 * KS + TN);
 }
 
-// The streaming form for a 1x1 / stride-1 layer with K = 64 or 128 (a: the
-// w32 view, Ntiles = ntiles32); form 0 plain, 1 statistics (ST), 2
-// BatchNorm-backward sums (BB).  -1: not served.
-static int m32s_dispatch(const ConvArgs& a, int tn32, float* part, const BnEpi& bb, int form,
-                         hipStream_t st) {
-  if (!m32s_on() || a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || a.tconv ||
-      a.nchw_in || a.x2 || a.ascale || a.y2 || a.Cin % kBK || a.M >= ((int64_t)1 << 31) - 64)
-    return -1;
-  const int KS = a.Cin / kBK;
-  if (KS != 2 && KS != 4) return -1;
+// Whether the streaming form serves a 1x1 / stride-1 layer with K = 64 or
+// 128, and with which (TN, KS): form 0 plain, 1 statistics (ST), 2
+// BatchNorm-backward sums (BB).  The route (conv.hip), both statistics entry
+// points and the launch below all ask here.
+bool m32s_pick(const ConvLayer& L, int form, int& TN, int& KS) {
+  const ConvArgs& a = L.a;
+  if (!m32s_on() || !L.is1x1 || a.tconv || a.nchw_in || a.x2 || a.ascale || a.y2 ||
+      a.Cin % kBK || a.M >= ((int64_t)1 << 31) - 64)
+    return false;
+  KS = a.Cin / kBK;
+  if (KS != 2 && KS != 4) return false;
   // K = 128: the plain form only by default (JABD_M32S_KS4 = mask of forms: bit 0 plain, 1
   // statistics, 2 BatchNorm-backward).  There TN = 2 (32 KiB of resident weights) re-reads the
   // pixels N / 64 times; the statistics form measured 463 (tile kernel) vs 479 us (l2.c3 at
   // bs16) and the C3 step 517.0-517.6 (plain only) vs 517.9-518.7 ms (all forms), r06/ab/ks4
-  {
-    static const int ks4 = [] {
-      const char* e = getenv("JABD_M32S_KS4");
-      return e ? atoi(e) : 1;
-    }();
-    static const int ks2 = [] {  // the same mask for K = 64 (all forms by default)
-      const char* e = getenv("JABD_M32S_KS2");
-      return e ? atoi(e) : 7;
-    }();
-    if (!(((KS == 4 ? ks4 : ks2) >> form) & 1)) return -1;
-  }
-  int TN = tn32;
+  static const int ks4 = (int)env_int("JABD_M32S_KS4", 1);
+  static const int ks2 = (int)env_int("JABD_M32S_KS2", 7);  // the same mask for K = 64
+  if (!(((KS == 4 ? ks4 : ks2) >> form) & 1)) return false;
+  TN = a.tn32;
   while (KS * TN > 8 && TN % 2 == 0) TN /= 2;  // resident weights <= 32 KiB
-  if (TN < 1 || KS * TN > 8 || a.Ntiles % TN) return -1;
+  // (every (TN, KS) within that bound is instantiated below)
+  return TN >= 1 && KS * TN <= 8 && a.ntiles32 % TN == 0;
+}
+
+// a: the w32 view; (TN, KS) from m32s_pick
+static int m32s_launch(const ConvArgs& a, int TN, int KS, int form, float* part, const BnEpi& bb,
+                       hipStream_t st) {
   // the plain form's epilogue terms, specialised when the layer has none or
   // only a residual (the R50 data gradients)
   const bool plain_none = !a.bias && !a.res && a.act == ACT_NONE;
   const bool plain_res = !a.bias && a.res && a.act == ACT_NONE;
 #define M32S(TN_, KS_)                                                                 \
+  if (TN == TN_ && KS == KS_)                                                          \
   return form == 1   ? launch_m32s<TN_, KS_, true, false, kEpiNone>(a, part, bb, st)   \
          : form == 2 ? launch_m32s<TN_, KS_, false, true, kEpiNone>(a, part, bb, st)   \
          : plain_none ? launch_m32s<TN_, KS_, false, false, kEpiNone>(a, part, bb, st) \
          : plain_res  ? launch_m32s<TN_, KS_, false, false, kEpiRes>(a, part, bb, st)  \
                       : launch_m32s<TN_, KS_, false, false, kEpiRt>(a, part, bb, st);
-  if (KS == 2) {
-    switch (TN) {
-      case 1: M32S(1, 2)
-      case 2: M32S(2, 2)
-      case 3: M32S(3, 2)
-      case 4: M32S(4, 2)
-      default: return -1;
-    }
-  }
-  switch (TN) {
-    case 1: M32S(1, 4)
-    case 2: M32S(2, 4)
-    default: return -1;
-  }
+  M32S(1, 2) M32S(2, 2) M32S(3, 2) M32S(4, 2) M32S(1, 4) M32S(2, 4)
 #undef M32S
+  return -1;
 }
 
 // Forward conv on the 32x32 kernel with the BatchNorm statistics rows (ST):
@@ -1133,17 +1101,14 @@ static int launch_m32_stats(const ConvArgs& a, float* part, const BnEpi& bb, hip
   return check_launch("conv1x1_m32 (BN statistics)", 100 + TN);
 }
 
-int conv_m32_stats_dispatch(const ConvArgs& a0, bool kxk, float* part, const BnEpi& bb,
+int conv_m32_stats_dispatch(const ConvLayer& L, bool kxk, float* part, const BnEpi& bb,
                             hipStream_t st) {
-  ConvArgs a = a0;
-  a.w = a0.w32;
-  a.Ntiles = a0.ntiles32;
-  if (!kxk) {
-    const int r = m32s_dispatch(a, a0.tn32, part, bb, bb.rows ? 2 : 1, st);
-    if (r >= 0) return r;
-  }
+  const ConvArgs a = L.view32();
+  const int form = bb.rows ? 2 : 1;
+  int tn, ks;
+  if (!kxk && m32s_pick(L, form, tn, ks)) return m32s_launch(a, tn, ks, form, part, bb, st);
 #define MS(TN_) return kxk ? launch_m32_stats<TN_, true>(a, part, bb, st) : launch_m32_stats<TN_, false>(a, part, bb, st);
-  switch (a0.tn32) {
+  switch (a.tn32) {
     case 1: MS(1)
     case 2: MS(2)
     case 3: MS(3)
@@ -1164,11 +1129,7 @@ using namespace jabd;
 // MNv3 +3%); the gate's per-workgroup weight scaling makes them slower on
 // the large gated GEMMs (C2's project convs).  JABD_M32_TM=1|2 forces one.
 static int m32_tm(const ConvArgs& a) {
-  static int ftm = -1;
-  if (ftm < 0) {
-    const char* e = getenv("JABD_M32_TM");
-    ftm = e ? atoi(e) : 0;
-  }
+  static const int ftm = (int)env_int("JABD_M32_TM", 0);
   if (a.tn32 > 4) return 1;
   if (ftm == 1 || ftm == 2) return ftm;
   return (!a.ascale || a.M < 65536) ? 1 : 2;
@@ -1182,35 +1143,49 @@ static int m32_tm(const ConvArgs& a) {
 // predict; its K-split already fills the device and 4x the workgroups each
 // re-read the pixel tile).  JABD_M32_TN1=0 keeps tn32 (A/B).
 static int m32_tn_launch(const ConvArgs& a) {
-  static const bool off = [] {
-    const char* e = getenv("JABD_M32_TN1");
-    return e && e[0] == '0';
-  }();
+  static const bool off = env_digit("JABD_M32_TN1") == 0;
   if (off || a.tn32 <= 1 || a.tconv || !a.ascale) return a.tn32;
-  const int64_t BM = 4 * 32 * m32_tm(a);
-  const int64_t OHW = (int64_t)a.OH * a.OW;
-  const int64_t mtiles = a.ascale ? cdiv(OHW, BM) * a.B : cdiv((int64_t)a.B * OHW, BM);
-  return mtiles * (a.ntiles32 / a.tn32) >= 256 ? a.tn32 : 1;
-}
-
-// The wave tiles (tm x tn) conv1x1_m32_dispatch launches a layer with: one
-// N-tile under the small-grid override, else the packing's tn32 at m32_tm.
-static void m32_tile(const ConvArgs& a, int& tm, int& tn) {
-  tn = m32_tn_launch(a);
-  tm = (tn == 1 && a.tn32 > 1) ? 1 : m32_tm(a);
+  return m32_grid(a, m32_tm(a), a.tn32) >= 256 ? a.tn32 : 1;
 }
 
 namespace jabd {
-// Split-K workspace bytes of a layer (a.M set) that jabd_conv2d_nhwc_f32
-// routes to conv1x1_m32_dispatch(a, st, kxk); 0: no split.  The tile choice,
-// the grid and the split come from the helpers the launch itself uses, so
-// the query (jabd_conv_workspace_size, conv.hip) and the launch cannot drift.
-// (K 64 / 128 1x1 layers on the streaming form have <= 4 stages: no split.)
-int64_t conv_m32_workspace_bytes(const ConvArgs& a, bool kxk) {
-  if (!a.w32 || a.tn32 <= 0 || a.tn32 > 7 || a.tconv || a.nchw_in) return 0;
-  int tm, tn;
-  m32_tile(a, tm, tn);
-  return m32_ksplit_bytes(a, m32_ksplit(a, kxk, m32_grid(a, tm, tn)));
+// Whether the tile kernel serves a layer use_conv32 (conv.hip) picked, as a
+// 1x1 (the fast-1x1 layout) or as a k x k implicit GEMM (32-channel stages
+// inside one tap), and with which wave tiles: one N tile under the small-grid
+// override, else the packing's tn32 at m32_tm (all of tm <= 2 x tn <= 4 and
+// 1 x 5..7 are instantiated).  ks: the K split the launch takes when the
+// caller's workspace holds conv_m32_ksplit_bytes(a, ks); the workspace query
+// reads the same ks.  (K 64 / 128 1x1 layers on the streaming form have <= 4
+// stages: no split.)
+bool m32_tile_pick(const ConvLayer& L, int& tm, int& tn, int& ks) {
+  const ConvArgs& a = L.a;
+  if (!L.w32(1, 7)) return false;
+  if (L.is1x1 ? !L.fast1x1
+              : !(L.v4out && !a.x2 && !a.y2 && L.kxk32() &&
+                  (!a.tconv || a.stride == 1 || (a.stride == 2 && !a.ascale))))
+    return false;
+  tn = m32_tn_launch(a);
+  tm = (tn == 1 && a.tn32 > 1) ? 1 : m32_tm(a);
+  ks = m32_ksplit(a, !L.is1x1, m32_grid(a, tm, tn));
+  return true;
+}
+
+int64_t conv_m32_ksplit_bytes(const ConvArgs& a, int ks) { return m32_ksplit_bytes(a, ks); }
+
+int conv_m32s_launch(const ConvLayer& L, const ConvRoute& r, hipStream_t st) {
+  return m32s_launch(L.view32(), r.tn, r.ks, 0, nullptr, BnEpi{}, st);
+}
+
+int conv_m32_tile_launch(const ConvLayer& L, const ConvRoute& r, hipStream_t st) {
+  const ConvArgs a = L.view32();
+  const bool kxk = !L.is1x1;
+#define M32(TM_, TN_)             \
+  if (r.tm == TM_ && r.tn == TN_) \
+    return kxk ? launch_m32<TM_, TN_, true>(a, r.ks, st) : launch_m32<TM_, TN_, false>(a, r.ks, st);
+  M32(1, 1) M32(1, 2) M32(1, 3) M32(1, 4) M32(2, 1) M32(2, 2) M32(2, 3) M32(2, 4)
+  M32(1, 5) M32(1, 6) M32(1, 7)
+#undef M32
+  return -1;
 }
 }  // namespace jabd
 
@@ -1225,30 +1200,6 @@ extern "C" int jabd_conv_pack_tn32(int cout) {
   }
   return best;
 }
-
-namespace jabd {
-// Called by jabd_conv2d_nhwc_f32 for 1x1 / stride-1 convs when the caller
-// supplied the 32x32 packing (args->w32).  Returns -1 when this kernel does
-// not take the shape (the caller then uses conv.hip).
-int conv1x1_m32_dispatch(const ConvArgs& a0, hipStream_t st, bool kxk) {
-  ConvArgs a = a0;
-  a.w = a0.w32;
-  a.Ntiles = a0.ntiles32;
-  if (!kxk) {  // K 64 / 128: the streaming form (no K split at <= 4 stages)
-    const int r = m32s_dispatch(a, a0.tn32, nullptr, BnEpi{}, 0, st);
-    if (r >= 0) return r;
-  }
-  int tm, tn;
-  m32_tile(a0, tm, tn);
-#define M32(TM_, TN_)         \
-  if (tm == TM_ && tn == TN_) \
-    return kxk ? launch_m32<TM_, TN_, true>(a, st) : launch_m32<TM_, TN_, false>(a, st);
-  M32(1, 1) M32(1, 2) M32(1, 3) M32(1, 4) M32(2, 1) M32(2, 2) M32(2, 3) M32(2, 4)
-  M32(1, 5) M32(1, 6) M32(1, 7)
-#undef M32
-  return -1;
-}
-}  // namespace jabd
 
 // ---------------------------------------------------------------------------
 // Weight packing on the device (the training convs repack after every
@@ -1270,43 +1221,54 @@ __device__ __forceinline__ float w2d_at(const float* __restrict__ w, int cout, i
   return w[((int64_t)co * cin + ci) * khw + tap];
 }
 
+// One float4 of wp: i = (kc * Ntiles + nt) * 64 + lane.
+__device__ __forceinline__ void pack_store16(const float* __restrict__ w, int cout, int cin,
+                                             int khw, int tr, int Ntiles, float* __restrict__ wp,
+                                             int64_t i) {
+  const int lane = (int)(i & 63);
+  const int64_t r = i >> 6;
+  const int nt = (int)(r % Ntiles), kc = (int)(r / Ntiles);
+  const int g = lane >> 4, j = lane & 15;
+  float4 v;
+  v.x = w2d_at(w, cout, cin, khw, tr, 16 * kc + 4 * g + 0, 16 * nt + j);
+  v.y = w2d_at(w, cout, cin, khw, tr, 16 * kc + 4 * g + 1, 16 * nt + j);
+  v.z = w2d_at(w, cout, cin, khw, tr, 16 * kc + 4 * g + 2, 16 * nt + j);
+  v.w = w2d_at(w, cout, cin, khw, tr, 16 * kc + 4 * g + 3, 16 * nt + j);
+  reinterpret_cast<float4*>(wp)[i] = v;
+}
+
+// One float4 of wp32: i = (k8 * NT32 + nt) * 64 + lane.
+__device__ __forceinline__ void pack_store32(const float* __restrict__ w, int cout, int cin,
+                                             int khw, int tr, int NT32, float* __restrict__ wp32,
+                                             int64_t i) {
+  const int lane = (int)(i & 63);
+  const int64_t r = i >> 6;
+  const int nt = (int)(r % NT32), k8 = (int)(r / NT32);
+  const int h = lane >> 5, j = lane & 31;
+  float4 v;
+  v.x = w2d_at(w, cout, cin, khw, tr, 8 * k8 + 4 * h + 0, 32 * nt + j);
+  v.y = w2d_at(w, cout, cin, khw, tr, 8 * k8 + 4 * h + 1, 32 * nt + j);
+  v.z = w2d_at(w, cout, cin, khw, tr, 8 * k8 + 4 * h + 2, 32 * nt + j);
+  v.w = w2d_at(w, cout, cin, khw, tr, 8 * k8 + 4 * h + 3, 32 * nt + j);
+  reinterpret_cast<float4*>(wp32)[i] = v;
+}
+
 __global__ __launch_bounds__(256) void pack_w_kernel(const float* __restrict__ w, int cout,
                                                      int cin, int khw, int transposed, int Kc,
                                                      int Ntiles, float* __restrict__ wp, int K8,
                                                      int NT32, float* __restrict__ wp32) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t n16 = (int64_t)Kc * Ntiles * 64;
-  if (i < n16) {
-    const int lane = (int)(i & 63);
-    const int64_t r = i >> 6;
-    const int nt = (int)(r % Ntiles), kc = (int)(r / Ntiles);
-    const int g = lane >> 4, j = lane & 15;
-    float4 v;
-    v.x = w2d_at(w, cout, cin, khw, transposed, 16 * kc + 4 * g + 0, 16 * nt + j);
-    v.y = w2d_at(w, cout, cin, khw, transposed, 16 * kc + 4 * g + 1, 16 * nt + j);
-    v.z = w2d_at(w, cout, cin, khw, transposed, 16 * kc + 4 * g + 2, 16 * nt + j);
-    v.w = w2d_at(w, cout, cin, khw, transposed, 16 * kc + 4 * g + 3, 16 * nt + j);
-    reinterpret_cast<float4*>(wp)[i] = v;
-    return;
-  }
-  const int64_t i2 = i - n16;
-  if (!wp32 || i2 >= (int64_t)K8 * NT32 * 64) return;
-  const int lane = (int)(i2 & 63);
-  const int64_t r = i2 >> 6;
-  const int nt = (int)(r % NT32), k8 = (int)(r / NT32);
-  const int h = lane >> 5, j = lane & 31;
-  float4 v;
-  v.x = w2d_at(w, cout, cin, khw, transposed, 8 * k8 + 4 * h + 0, 32 * nt + j);
-  v.y = w2d_at(w, cout, cin, khw, transposed, 8 * k8 + 4 * h + 1, 32 * nt + j);
-  v.z = w2d_at(w, cout, cin, khw, transposed, 8 * k8 + 4 * h + 2, 32 * nt + j);
-  v.w = w2d_at(w, cout, cin, khw, transposed, 8 * k8 + 4 * h + 3, 32 * nt + j);
-  reinterpret_cast<float4*>(wp32)[i2] = v;
+  if (i < n16)
+    pack_store16(w, cout, cin, khw, transposed, Ntiles, wp, i);
+  else if (wp32 && i - n16 < (int64_t)K8 * NT32 * 64)
+    pack_store32(w, cout, cin, khw, transposed, NT32, wp32, i - n16);
 }
 
 // Batched pack: one launch for every weight an optimizer step changed.  Job
 // rows {w, wp, wp32, cout, cin, khw, transposed, Kc, Ntiles, K8, NT32};
 // starts[i] = float4 outputs of jobs < i, staged in LDS for a binary search.
-constexpr int kPackMaxJobs = 1024;
+constexpr int kPackMaxJobs = 1024;  // = REPACK_MAX_JOBS (jabd_amd/train.py)
 __global__ __launch_bounds__(256) void pack_w_multi_kernel(const int64_t* __restrict__ jobs,
                                                            const int64_t* __restrict__ starts,
                                                            int njobs, int64_t total) {
@@ -1328,30 +1290,10 @@ __global__ __launch_bounds__(256) void pack_w_multi_kernel(const int64_t* __rest
   const int Kc = (int)jb[7], Ntiles = (int)jb[8], NT32 = (int)jb[10];
   const int64_t r0 = i - st[lo];
   const int64_t n16 = (int64_t)Kc * Ntiles * 64;
-  if (r0 < n16) {
-    const int lane = (int)(r0 & 63);
-    const int64_t r = r0 >> 6;
-    const int nt = (int)(r % Ntiles), kc = (int)(r / Ntiles);
-    const int g = lane >> 4, j = lane & 15;
-    float4 v;
-    v.x = w2d_at(w, cout, cin, khw, tr, 16 * kc + 4 * g + 0, 16 * nt + j);
-    v.y = w2d_at(w, cout, cin, khw, tr, 16 * kc + 4 * g + 1, 16 * nt + j);
-    v.z = w2d_at(w, cout, cin, khw, tr, 16 * kc + 4 * g + 2, 16 * nt + j);
-    v.w = w2d_at(w, cout, cin, khw, tr, 16 * kc + 4 * g + 3, 16 * nt + j);
-    reinterpret_cast<float4*>(wp)[r0] = v;
-    return;
-  }
-  const int64_t i2 = r0 - n16;
-  const int lane = (int)(i2 & 63);
-  const int64_t r = i2 >> 6;
-  const int nt = (int)(r % NT32), k8 = (int)(r / NT32);
-  const int h = lane >> 5, j = lane & 31;
-  float4 v;
-  v.x = w2d_at(w, cout, cin, khw, tr, 8 * k8 + 4 * h + 0, 32 * nt + j);
-  v.y = w2d_at(w, cout, cin, khw, tr, 8 * k8 + 4 * h + 1, 32 * nt + j);
-  v.z = w2d_at(w, cout, cin, khw, tr, 8 * k8 + 4 * h + 2, 32 * nt + j);
-  v.w = w2d_at(w, cout, cin, khw, tr, 8 * k8 + 4 * h + 3, 32 * nt + j);
-  reinterpret_cast<float4*>(wp32)[i2] = v;
+  if (r0 < n16)
+    pack_store16(w, cout, cin, khw, tr, Ntiles, wp, r0);
+  else
+    pack_store32(w, cout, cin, khw, tr, NT32, wp32, r0 - n16);
 }
 
 }  // namespace jabd

@@ -268,12 +268,8 @@ __global__ __launch_bounds__((CsCfg<TN, KC>::NW * 64)) void conv1x1_stream_kerne
 
 // JABD_CONV_STREAM=0 disables the streaming kernel (A/B).
 static bool conv_stream_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("JABD_CONV_STREAM");
-    v = e && e[0] == '0' ? 0 : 1;
-  }
-  return v == 1;
+  static const bool on = env_digit("JABD_CONV_STREAM") != 0;
+  return on;
 }
 
 static int stream_kc(int kc) {
@@ -295,38 +291,66 @@ static int stream_grid(Kern kern, int threads, size_t lds, int64_t nwg) {
   return (int)(nwg < cap ? nwg : cap);
 }
 
-// Called from jabd_conv2d_nhwc_f32 for the fast-1x1 layouts (contiguous NHWC
-// rows, v4 epilogue, x2 at the same resolution).  Returns -1 when the shape is
-// not one this kernel serves.
-// ss != nullptr: the statistics form (ST; no gate, no second source, no
-// residual).  ss->query: only report the grid (= partial rows) in ss->nblk;
-// otherwise launch and require ss->nblk to match it.
-int conv1x1_stream_dispatch(const ConvArgs& a, hipStream_t st, StreamStats* ss) {
-  if (!conv_stream_on()) return -1;
-  if (ss && (a.x2 || a.ascale || a.res || stream_kc(a.Kc) > 4)) return -1;
+// The (TN, KC) instances of the plain form; the statistics form has those
+// with KC <= 4.  One list for the predicate and the launcher.
+#define CS_ROW(X, TN_) X(TN_, 1) X(TN_, 2) X(TN_, 3) X(TN_, 4) X(TN_, 5) X(TN_, 6) X(TN_, 8)
+#define CS_INSTANCES(X)                                          \
+  CS_ROW(X, 1) CS_ROW(X, 2) CS_ROW(X, 3) CS_ROW(X, 4) CS_ROW(X, 5) \
+  X(2, 10) X(3, 10) X(3, 12) X(5, 10) X(5, 12) X(5, 13) X(5, 16) X(5, 18)
+#define CS_STATS_INSTANCES(X)                                                           \
+  X(1, 1) X(2, 1) X(3, 1) X(4, 1) X(5, 1) X(1, 2) X(2, 2) X(3, 2) X(4, 2) X(5, 2) \
+  X(1, 3) X(2, 3) X(3, 3) X(4, 3) X(5, 3) X(1, 4) X(2, 4) X(3, 4) X(4, 4) X(5, 4)
+
+// Whether this kernel serves a layer of the fast-1x1 layouts (contiguous NHWC
+// rows, v4 epilogue, x2 at the same resolution); stats: its statistics form
+// (no gate, no second source, no residual).  The route (conv.hip) and the
+// dispatch below both ask here; only the occupancy query of the launch can
+// still turn a served layer away.
+bool conv1x1_stream_serves(const ConvArgs& a, bool stats) {
+  if (!conv_stream_on()) return false;
+  if (stats && (a.x2 || a.ascale || a.res || stream_kc(a.Kc) > 4)) return false;
   const int TN = a.Ntiles, KC = stream_kc(a.Kc);
-  if (TN < 1 || TN > 5 || KC < 0) return -1;
-  if (a.x2 && a.x2_stride != 1) return -1;
+  if (TN < 1 || TN > 5 || KC < 0) return false;
+  if (a.x2 && a.x2_stride != 1) return false;
   const int64_t ohw = (int64_t)a.OH * a.OW;
-  if (a.ascale && (ohw % 16 || a.ascale_bs % 4)) return -1;
+  if (a.ascale && (ohw % 16 || a.ascale_bs % 4)) return false;
   const size_t lds = (size_t)a.Kc * TN * 1024 + (a.ascale ? (size_t)a.B * a.Cin * 4 : 0);
-  if (lds > (a.Kc * TN > 24 ? 150 : 40) * 1024) return -1;
-  const int64_t nblk = cdiv(a.M, 16);
-  if (nblk >= ((int64_t)1 << 27)) return -1;
+  if (lds > (a.Kc * TN > 24 ? 150 : 40) * 1024) return false;
+  if (cdiv(a.M, 16) >= ((int64_t)1 << 27)) return false;
   // the kernel forms pixel offsets m * ps in 32-bit ints (the caller's fast1x1
   // condition already bounds (M + 64) * (max ps + 16) < 2^31; kept here so the
   // kernel never relies on a caller's check)
   const int64_t maxps = std::max<int64_t>(std::max<int64_t>(a.x_ps, a.y_ps),
                                           std::max<int64_t>(a.res ? a.res_ps : 0,
                                                             a.x2 ? a.x2_ps : 0));
-  if ((a.M + 16) * (maxps + 16) >= ((int64_t)1 << 31)) return -1;
+  if ((a.M + 16) * (maxps + 16) >= ((int64_t)1 << 31)) return false;
+  // the instance's wave count (CsCfg, from the rounded KC) must be the one the
+  // LDS bound above assumed (from Kc)
+  if ((a.Kc * TN > 24) != (KC * TN > 24)) return false;
+#define CS_HAS(TN_, KC_) \
+  if (TN == TN_ && KC == KC_) return true;
+  CS_INSTANCES(CS_HAS)
+#undef CS_HAS
+  return false;
+}
+
+// Called from jabd_conv2d_nhwc_f32 for the layers conv1x1_stream_serves takes.
+// Returns -1 when the shape is not served.
+// ss != nullptr: the statistics form (ST).  ss->query: only report the grid
+// (= partial rows) in ss->nblk; otherwise launch and require ss->nblk to
+// match it.
+int conv1x1_stream_dispatch(const ConvArgs& a, hipStream_t st, StreamStats* ss) {
+  if (!conv1x1_stream_serves(a, ss != nullptr)) return -1;
+  const int TN = a.Ntiles, KC = stream_kc(a.Kc);
+  const int64_t ohw = (int64_t)a.OH * a.OW;
+  const size_t lds = (size_t)a.Kc * TN * 1024 + (a.ascale ? (size_t)a.B * a.Cin * 4 : 0);
+  const int64_t nblk = cdiv(a.M, 16);
   const int x2 = a.x2 ? 1 : 0;
   const bool as = a.ascale != nullptr;
 #define CS_LAUNCH(TN_, KC_, X2_, AS_)                                                       \
   do {                                                                                      \
     auto kern = conv1x1_stream_kernel<TN_, KC_, X2_, AS_>;                                  \
     constexpr int nw_ = CsCfg<TN_, KC_>::NW;                                                \
-    if ((a.Kc * TN > 24) != (nw_ == 8)) return -1;                                          \
     const int grid = stream_grid(kern, nw_ * 64, lds, cdiv(nblk, nw_));                     \
     if (grid < 1) return -1;                                                                \
     kern<<<grid, nw_ * 64, lds, st>>>(a, (int)nblk, (int)ohw, nullptr, nullptr);            \
@@ -336,7 +360,6 @@ int conv1x1_stream_dispatch(const ConvArgs& a, hipStream_t st, StreamStats* ss) 
   do {                                                                                      \
     auto kern = conv1x1_stream_kernel<TN_, KC_, 0, false, true>;                            \
     constexpr int nw_ = CsCfg<TN_, KC_>::NW;                                                \
-    if ((a.Kc * TN > 24) != (nw_ == 8)) return -1;                                          \
     const int grid = stream_grid(kern, nw_ * 64, lds, cdiv(nblk, nw_));                     \
     if (grid < 1) return -1;                                                                \
     if (ss->query) {                                                                        \
@@ -351,10 +374,7 @@ int conv1x1_stream_dispatch(const ConvArgs& a, hipStream_t st, StreamStats* ss) 
   } while (0)
 #define CS_FLAGS_ST(TN_, KC_) \
   if (ss && TN == TN_ && KC == KC_) CS_LAUNCH_ST(TN_, KC_);
-  CS_FLAGS_ST(1, 1) CS_FLAGS_ST(2, 1) CS_FLAGS_ST(3, 1) CS_FLAGS_ST(4, 1) CS_FLAGS_ST(5, 1)
-  CS_FLAGS_ST(1, 2) CS_FLAGS_ST(2, 2) CS_FLAGS_ST(3, 2) CS_FLAGS_ST(4, 2) CS_FLAGS_ST(5, 2)
-  CS_FLAGS_ST(1, 3) CS_FLAGS_ST(2, 3) CS_FLAGS_ST(3, 3) CS_FLAGS_ST(4, 3) CS_FLAGS_ST(5, 3)
-  CS_FLAGS_ST(1, 4) CS_FLAGS_ST(2, 4) CS_FLAGS_ST(3, 4) CS_FLAGS_ST(4, 4) CS_FLAGS_ST(5, 4)
+  CS_STATS_INSTANCES(CS_FLAGS_ST)
   if (ss) return -1;
 #undef CS_FLAGS_ST
 #undef CS_LAUNCH_ST
@@ -365,13 +385,7 @@ int conv1x1_stream_dispatch(const ConvArgs& a, hipStream_t st, StreamStats* ss) 
     if (x2 == 1 && !as) CS_LAUNCH(TN_, KC_, 1, false); \
     CS_LAUNCH(TN_, KC_, 1, true);               \
   }
-#define CS_KC(TN_) \
-  CS_FLAGS(TN_, 1) CS_FLAGS(TN_, 2) CS_FLAGS(TN_, 3) CS_FLAGS(TN_, 4) CS_FLAGS(TN_, 5) \
-  CS_FLAGS(TN_, 6) CS_FLAGS(TN_, 8)
-  CS_KC(1) CS_KC(2) CS_KC(3) CS_KC(4) CS_KC(5)
-  CS_FLAGS(2, 10) CS_FLAGS(3, 10) CS_FLAGS(3, 12)
-  CS_FLAGS(5, 10) CS_FLAGS(5, 12) CS_FLAGS(5, 13) CS_FLAGS(5, 16) CS_FLAGS(5, 18)
-#undef CS_KC
+  CS_INSTANCES(CS_FLAGS)
 #undef CS_FLAGS
 #undef CS_LAUNCH
   return -1;

@@ -405,10 +405,7 @@ static int dwconv_stats(const jabd_dw_args* args, float* stats_part, float* shif
   hipStream_t st = as_stream(stream);
   // 3x3: the row walker, within the same partial-block count
   // (JABD_DW_ROWS=0: dw_kernel)
-  static const bool rows_on = [] {
-    const char* e = getenv("JABD_DW_ROWS");
-    return !(e && e[0] == '0');
-  }();
+  static const bool rows_on = env_digit("JABD_DW_ROWS") != 0;
 #define DWR_CASE(S, PW)                                                                      \
   if (rows_on && a.k == 3 && a.stride == S && a.pad == 1) {                                 \
     const int SP = kDwThreads / (a.C / 4);                                                   \

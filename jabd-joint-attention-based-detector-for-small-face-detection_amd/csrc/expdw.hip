@@ -857,12 +857,8 @@ using namespace jabd;
 // DESIGN.md section 4).  JABD_EXPDW_WS=1 or jabd_expand_dw_select(2) selects it.
 static int xw_form = 0;  // jabd_expand_dw_select
 static bool xw_enabled() {
-  static int env = -1;
-  if (env < 0) {
-    const char* e = getenv("JABD_EXPDW_WS");
-    env = e && e[0] == '1' ? 1 : 0;
-  }
-  return xw_form ? xw_form == 2 : env == 1;
+  static const bool env = env_digit("JABD_EXPDW_WS") == 1;
+  return xw_form ? xw_form == 2 : env;
 }
 
 template <int K, int S, int TH, int TW, int EC, int ACT, bool SKIP>

@@ -741,11 +741,7 @@ extern "C" int jabd_nlm_apply_f32(const float* src, int64_t src_bs, int32_t src_
   const size_t smem = (2 * (size_t)S * ch + 2 * (size_t)ch * C + C) * sizeof(float);
   JABD_REQUIRE(smem <= 64 * 1024, "nlm_apply: LDS %zu > 64KiB", smem);
   // JABD_NLM_PX=1: one pixel per quad (A/B)
-  static int px = -1;
-  if (px < 0) {
-    const char* e = getenv("JABD_NLM_PX");
-    px = e && e[0] == '1' ? 1 : 2;
-  }
+  static const int px = env_digit("JABD_NLM_PX") == 1 ? 1 : 2;
   if (px == 2) {
     dim3 g((unsigned)cdiv((int64_t)h * w, 128), (unsigned)B);  // a quad of lanes per 2 pixels
     nlm_apply_kernel<4, 2><<<g, 256, smem, as_stream(stream)>>>(src, src_bs, src_ps, hs, ws, C, h,

@@ -481,10 +481,7 @@ extern "C" int jabd_nlm_bwd_attn_f32(const float* dout, int32_t B, int32_t h, in
                "nlm_bwd_attn: bad args");
   hipStream_t st = as_stream(stream);
   // JABD_NLM_BWD_QUAD=1: the lane-quad kernel (A/B)
-  static const bool quad = [] {
-    const char* e = getenv("JABD_NLM_BWD_QUAD");
-    return e && e[0] == '1';
-  }();
+  static const bool quad = env_digit("JABD_NLM_BWD_QUAD") == 1;
   if (!quad) {
     const int nblk = (int)cdiv((int64_t)h * w, 256);  // within jabd.h's part size (64-pixel blocks)
     const size_t smem = (2 * (size_t)C * CH + 2 * 256 * CH + 2 * (size_t)kNb * kNbP +

@@ -61,12 +61,8 @@ static constexpr int kMaxImg = 254;  // 255 marks a filtered-out row
 
 // JABD_NMS_DENSE=1 disables the grid producer (A/B tests and measurement).
 static bool nms_dense_only() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("JABD_NMS_DENSE");
-    v = e && e[0] == '1' ? 1 : 0;
-  }
-  return v == 1;
+  static const bool v = env_digit("JABD_NMS_DENSE") == 1;
+  return v;
 }
 
 // Images with at most this many candidates take the dense all-pairs mask even
@@ -81,19 +77,12 @@ static bool nms_dense_only() {
 // mask they could save).  JABD_NMS_DENSE_ROWS=<n> for A/B (0 = grid whenever
 // possible).
 static int64_t nms_dense_rows() {
-  static const int64_t v = [] {
-    const char* e = getenv("JABD_NMS_DENSE_ROWS");
-    return e ? (int64_t)atoll(e) : (int64_t)20480;
-  }();
+  static const int64_t v = env_int("JABD_NMS_DENSE_ROWS", 20480);
   return v;
 }
 
 static int nms_dense_max() {
-  static int v = -2;
-  if (v == -2) {
-    const char* e = getenv("JABD_NMS_DENSE_MAX");
-    v = e ? atoi(e) : 8192;
-  }
+  static const int v = (int)env_int("JABD_NMS_DENSE_MAX", 8192);
   return v;
 }
 
@@ -507,8 +496,7 @@ static constexpr int64_t kOvfPerBox = 16;
 // the overflow region off between calls; the size query and the call it
 // sizes must see the same value)
 static int64_t nms_ovf_per_box() {
-  const char* e = getenv("JABD_NMS_OVF_PER_BOX");
-  return e ? std::max<int64_t>(0, atoll(e)) : kOvfPerBox;
+  return std::max<int64_t>(0, env_int("JABD_NMS_OVF_PER_BOX", kOvfPerBox));
 }
 static constexpr int kK = 2;                  // class sub-division (neighbour range)
 static constexpr int kGridNbr = 1 + kK + kK * (2 * kK + 1);  // class pairs searched per box

@@ -493,10 +493,7 @@ static void carve_radix(A& a, int64_t n, bool vals, RadixWs* w) {
 
 // JABD_RADIX_SMALL=0: every size takes the multi-workgroup passes (A/B)
 static bool radix_small_off() {
-  static const bool off = [] {
-    const char* e = getenv("JABD_RADIX_SMALL");
-    return e && e[0] == '0';
-  }();
+  static const bool off = env_digit("JABD_RADIX_SMALL") == 0;
   return off;
 }
 

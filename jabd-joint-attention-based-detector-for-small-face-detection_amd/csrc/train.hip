@@ -1198,13 +1198,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad32_kernel(const ConvArgs p, 
 // The 32x32 wgrad kernel takes NHWC/vector shapes with K, Cout >= 64;
 // JABD_WGRAD32=0 forces the 16x16x4 kernels (A/B).
 static bool wgrad32_ok(const ConvArgs& a) {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("JABD_WGRAD32");
-    v = e && e[0] == '0' ? 0 : 1;
-  }
+  static const bool on = env_digit("JABD_WGRAD32") != 0;
   const int64_t K = (int64_t)a.KH * a.KW * a.Cin;
-  return v == 1 && K >= 64 && a.Cout >= 64;
+  return on && K >= 64 && a.Cout >= 64;
 }
 // 128-wide tiles unless they pad more than 1/8 beyond what 64-wide ones do
 static int wg32_tile(int64_t n) { return cdiv(n, 128) * 128 - n <= n / 8 ? 128 : 64; }
@@ -2362,10 +2358,7 @@ int stem7_wgrad_launch(const ConvArgs& a, float* part, hipStream_t st);
 
 // ResNet-50 7x7/s2 stem (stem7.hip); JABD_STEM7=0 -> the tiled kernels
 static bool stem7_wgrad_on(const ConvArgs& a) {
-  static const bool on = [] {
-    const char* e = getenv("JABD_STEM7");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_digit("JABD_STEM7") != 0;
   return on && stem7_ok(a) && a.y_ps % 4 == 0 && a.y_c0 % 4 == 0 && a.y_bs % 4 == 0 &&
          (reinterpret_cast<uintptr_t>(a.y) & 15) == 0;
 }
@@ -2645,10 +2638,7 @@ extern "C" int jabd_dw_dgrad_bn_bwd_f32(const float* dy, const float* w, int32_t
   // strip-row kernel at every C4 shape (b1 s2 1803 -> 2640 us, b3 647 -> 1017,
   // b7 181 -> 205: ~200 VGPRs, two waves per SIMD, where the strip-row
   // kernel's dy re-reads hit L2)
-  static const bool rows_on = [] {
-    const char* e = getenv("JABD_DW_DGRAD_ROWS");
-    return e && e[0] == '1';
-  }();
+  static const bool rows_on = env_digit("JABD_DW_DGRAD_ROWS") == 1;
   const int rows_pass = 256 / lanes;
 #define DGR_CASE(S_, PW_)                                                                      \
   if (rows_on && k == 3 && stride == S_) {                                                     \
@@ -2737,10 +2727,7 @@ static int dw_wgrad(const float* x, const float* dy, int32_t B, int32_t H, int32
   int64_t nblk = 0;
   // 3x3: the row-walking kernel when (image, band) pairs leave room for row
   // chunks within the 1024 partial blocks (JABD_DW_WGRAD_ROWS=0: strip kernel)
-  static const bool rows_on = [] {
-    const char* e = getenv("JABD_DW_WGRAD_ROWS");
-    return !(e && e[0] == '0');
-  }();
+  static const bool rows_on = env_digit("JABD_DW_WGRAD_ROWS") != 0;
 #define WR_CASE(S_, PW_)                                                                        \
   if (rows_on && k == 3 && stride == S_) {                                                      \
     const int nstrip = (int)cdiv(OW, PW_);                                                      \
