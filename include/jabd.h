@@ -362,6 +362,56 @@ int jabd_multibox_diou_loss_bwd_f32(const float* loc, const float* conf,
                                     const int64_t* counts, float* grad_loc,
                                     float* grad_conf, float* grad_landm,
                                     jabd_stream_t stream);
+/* The IoU-family MultiBoxLoss — the same module's IouLoss(losstype) as the
+ * box term (:491-522).  The arguments of the DIoU pair followed by kind;
+ * b1 = decode(loc, prior), b2 = loc_t, I/U their intersection and union,
+ * ow/oh the extents of their enclosing box (each clamped at 0):
+ *   kind 0  Iou   I/U, clamped to [0, 1]                          (:339-365)
+ *   kind 1  Giou  I/U - (C - U)/C with C = ow*oh, to [-1, 1]      (:366-401)
+ *   kind 2  Diou  I/U - rho2/c2, to [-1, 1] — the pair above       (:402-442)
+ *   kind 3  Ciou  I/U - (rho2/c2 + alpha*v), to [-1, 1]           (:444-490)
+ *           v = 4/pi^2 (atan(w2/h2) - atan(w1/h1))^2,
+ *           alpha = v / ((1 - I/U) + v), a constant in the backward (the
+ *           reference computes it under no_grad).  A prediction bit-equal
+ *           to its truth gives alpha = 0/0: value and gradient are NaN, as
+ *           the reference's.
+ * sums[0] is Σ over positives of 1 - clamp(value).  The backward is analytic:
+ * the clamp passes the gradient on its closed interval, clamp(min=0) on an
+ * extent where the raw extent is >= 0, and a min/max tie gives half to each
+ * side.  Any other kind is JABD_EINVAL.  The same launches and workspace as
+ * the DIoU pair, which is these two with kind 2. */
+int jabd_multibox_iou_loss_fwd_f32(const float* loc, const float* conf,
+                                   const float* landm, const float* loc_t,
+                                   const int64_t* conf_t, const float* landm_t,
+                                   const float* priors, float var0, float var1,
+                                   int64_t batch, int64_t num_priors, int neg_pos,
+                                   float* sums, int64_t* counts, uint8_t* sel,
+                                   void* ws, size_t ws_bytes, int32_t kind,
+                                   jabd_stream_t stream);
+int jabd_multibox_iou_loss_bwd_f32(const float* loc, const float* conf,
+                                   const float* landm, const float* loc_t,
+                                   const int64_t* conf_t, const float* landm_t,
+                                   const float* priors, float var0, float var1,
+                                   const uint8_t* sel, int64_t batch,
+                                   int64_t num_priors, const float* gout,
+                                   const int64_t* counts, float* grad_loc,
+                                   float* grad_conf, float* grad_landm,
+                                   int32_t kind, jabd_stream_t stream);
+/* The paired overlaps on their own — bbox_overlaps_iou/giou/diou/ciou for
+ * rows == cols (:339-490): val[i] = the clamped kind-overlap of prediction i
+ * against truth[i] ([n,4] corners).  priors NULL: pred [n,4] holds corner
+ * boxes; otherwise pred holds loc offsets decoded against priors [n,4]
+ * (cx,cy,w,h; one prior per row) with var0/var1 (IouLoss pred_mode 'Center').
+ * The backward writes gpred[n,4] = gval[i] * d val[i] / d pred[i] with the
+ * conventions above.  One row per thread, no atomics; n == 0 succeeds
+ * without a launch. */
+int jabd_iou_rows_fwd_f32(const float* pred, const float* priors,
+                          const float* truth, int64_t n, float var0, float var1,
+                          int32_t kind, float* val, jabd_stream_t stream);
+int jabd_iou_rows_bwd_f32(const float* pred, const float* priors,
+                          const float* truth, int64_t n, float var0, float var1,
+                          int32_t kind, const float* gval, float* gpred,
+                          jabd_stream_t stream);
 /* loss[i] = sums[i] / max(counts[i==2 ? 1 : 0], 1)  (device, 1 thread). */
 int jabd_multibox_loss_finalize_f32(const float* sums, const int64_t* counts,
                                     float* loss, jabd_stream_t stream);

@@ -254,70 +254,126 @@ __device__ __forceinline__ float smooth_l1(float d) {
 }
 
 // ---------------------------------------------------------------------------
-// DIoU box term — nets/retinaface_training_DIOU.py: IouLoss 'Diou' (:491-522)
-// over decode() (:319-337) and bbox_overlaps_diou (:402-442), paired rows:
-//   1 - clamp(I/U - |c2-c1|^2 / |outer|^2, -1, 1)
+// IoU-family box terms — nets/retinaface_training_DIOU.py: IouLoss (:491-522)
+// over decode() (:319-337) and bbox_overlaps_iou/giou/diou/ciou (:339-490),
+// paired rows, b1 = the prediction, b2 = the truth:
+//   kBoxIou   I/U                                   clamp [0, 1]
+//   kBoxGiou  I/U - (C - U)/C, C = ow*oh            clamp [-1, 1]
+//   kBoxDiou  I/U - |c2-c1|^2 / |outer|^2           clamp [-1, 1]
+//   kBoxCiou  I/U - (|c2-c1|^2/|outer|^2 + a*v)     clamp [-1, 1]
+//             v = 4/pi^2 (atan(w2/h2) - atan(w1/h1))^2, a = v/((1 - I/U) + v),
+//             a constant in the backward (the reference's no_grad block)
+// and the per-row loss is 1 - clamp(value).  kBoxSmoothL1 names the base
+// loss's box term in the fused kernels' template parameter.
 // ---------------------------------------------------------------------------
-struct DiouTerms {
-  Box4 b;                                  // decoded prediction (bboxes1)
+constexpr int kBoxSmoothL1 = -1, kBoxIou = 0, kBoxGiou = 1, kBoxDiou = 2, kBoxCiou = 3;
+
+struct IouTerms {
+  Box4 b;                                  // prediction corners (bboxes1)
   float w1, h1, iwr, ihr, iw, ih, inter;   // iwr/ihr before clamp(min=0)
   float dcx, dcy, diag, owr, ohr, ow, oh, odiag, uni, d;
+  float carea;                             // Giou: the closure's area
+  float dat, alpha;                        // Ciou: atan(w2/h2) - atan(w1/h1), a
 };
 
-__device__ __forceinline__ DiouTerms diou_terms(const float4 l, const float4 p, const float4 t,
-                                                float v0, float v1) {
-  const float la[4] = {l.x, l.y, l.z, l.w};
-  DiouTerms r;
-  r.b = decode_one(la, p, v0, v1);
-  const Box4 b = r.b;
+template <int kKind>
+__device__ __forceinline__ IouTerms iou_terms(const Box4 b, const float4 t) {
+  IouTerms r;
+  r.b = b;
   r.w1 = b.x2 - b.x1;
   r.h1 = b.y2 - b.y1;
   const float w2 = t.z - t.x, h2 = t.w - t.y;
   const float area1 = r.w1 * r.h1, area2 = w2 * h2;
-  const float cx1 = (b.x2 + b.x1) / 2.f, cy1 = (b.y2 + b.y1) / 2.f;
-  const float cx2 = (t.z + t.x) / 2.f, cy2 = (t.w + t.y) / 2.f;
   r.iwr = nan_min(b.x2, t.z) - nan_max(b.x1, t.x);
   r.ihr = nan_min(b.y2, t.w) - nan_max(b.y1, t.y);
   r.iw = nan_max(r.iwr, 0.f);
   r.ih = nan_max(r.ihr, 0.f);
   r.inter = r.iw * r.ih;
-  r.dcx = cx2 - cx1;
-  r.dcy = cy2 - cy1;
-  r.diag = r.dcx * r.dcx + r.dcy * r.dcy;
-  r.owr = nan_max(b.x2, t.z) - nan_min(b.x1, t.x);
-  r.ohr = nan_max(b.y2, t.w) - nan_min(b.y1, t.y);
-  r.ow = nan_max(r.owr, 0.f);
-  r.oh = nan_max(r.ohr, 0.f);
-  r.odiag = r.ow * r.ow + r.oh * r.oh;
+  if (kKind != kBoxIou) {
+    r.owr = nan_max(b.x2, t.z) - nan_min(b.x1, t.x);
+    r.ohr = nan_max(b.y2, t.w) - nan_min(b.y1, t.y);
+    r.ow = nan_max(r.owr, 0.f);
+    r.oh = nan_max(r.ohr, 0.f);
+  }
+  if (kKind == kBoxDiou || kKind == kBoxCiou) {
+    const float cx1 = (b.x2 + b.x1) / 2.f, cy1 = (b.y2 + b.y1) / 2.f;
+    const float cx2 = (t.z + t.x) / 2.f, cy2 = (t.w + t.y) / 2.f;
+    r.dcx = cx2 - cx1;
+    r.dcy = cy2 - cy1;
+    r.diag = r.dcx * r.dcx + r.dcy * r.dcy;
+    r.odiag = r.ow * r.ow + r.oh * r.oh;
+  }
   r.uni = area1 + area2 - r.inter;
-  r.d = r.inter / r.uni - r.diag / r.odiag;
+  if (kKind == kBoxIou) {
+    r.d = r.inter / r.uni;
+  } else if (kKind == kBoxGiou) {
+    r.carea = r.ow * r.oh;
+    r.d = r.inter / r.uni - (r.carea - r.uni) / r.carea;
+  } else if (kKind == kBoxDiou) {
+    r.d = r.inter / r.uni - r.diag / r.odiag;
+  } else {
+    const float u = r.diag / r.odiag;
+    const float iou = r.inter / r.uni;
+    r.dat = atanf(w2 / h2) - atanf(r.w1 / r.h1);
+    const float v = 0.40528473456935116f * (r.dat * r.dat);  // 4 / pi^2
+    const float S = 1.f - iou;
+    r.alpha = v / (S + v);
+    r.d = iou - (u + r.alpha * v);
+  }
   return r;
 }
 
-__device__ __forceinline__ float diou_loss(const float4 l, const float4 p, const float4 t,
-                                           float v0, float v1) {
-  const float d = diou_terms(l, p, t, v0, v1).d;
-  return 1.f - fminf(fmaxf(d, -1.f), 1.f);
+// torch.clamp(d, lo, 1): lo = 0 for Iou, -1 otherwise.  A NaN stays NaN, as
+// torch's does; the DIoU instantiation keeps the form it shipped with.
+template <int kKind>
+__device__ __forceinline__ float iou_clamp(float d) {
+  const float c = fminf(fmaxf(d, kKind == kBoxIou ? 0.f : -1.f), 1.f);
+  return (kKind != kBoxDiou && d != d) ? d : c;
+}
+
+__device__ __forceinline__ Box4 decode_box(const float4 l, const float4 p, float v0, float v1) {
+  const float la[4] = {l.x, l.y, l.z, l.w};
+  return decode_one(la, p, v0, v1);
+}
+
+template <int kKind>
+__device__ __forceinline__ float iou_loss(const float4 l, const float4 p, const float4 t,
+                                          float v0, float v1) {
+  const float d = iou_terms<kKind>(decode_box(l, p, v0, v1), t).d;
+  return 1.f - iou_clamp<kKind>(d);
 }
 
 // torch.minimum/maximum backward: the whole gradient to the winner, half each on a tie.
 __device__ __forceinline__ float pick_lo(float a, float b) { return a < b ? 1.f : (a == b ? .5f : 0.f); }
 __device__ __forceinline__ float pick_hi(float a, float b) { return a > b ? 1.f : (a == b ? .5f : 0.f); }
 
-// d(loss)/d(loc) for one positive, scaled by s (= dL/dloss_l / N).
-__device__ __forceinline__ float4 diou_grad(const float4 l, const float4 p, const float4 t,
-                                            float v0, float v1, float s) {
-  const DiouTerms r = diou_terms(l, p, t, v0, v1);
-  float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (!(r.d >= -1.f && r.d <= 1.f)) return g;  // clamp() passes the gradient on [-1, 1]
-  const float gd = -s;
+// Gradient with respect to the prediction's corners (x1, y1, x2, y2) given
+// gd = dL/d(clamped value).  clamp() passes the gradient on its closed interval.
+template <int kKind>
+__device__ __forceinline__ float4 iou_box_grad(const IouTerms& r, const float4 t, float gd) {
+  const bool inside = r.d >= (kKind == kBoxIou ? 0.f : -1.f) && r.d <= 1.f;
+  if (kKind == kBoxCiou) {
+    // autograd's clamp backward zeroes gd outside the interval and the chain
+    // goes on: with a = 0/0 (prediction == truth) 0 * a makes the gradient NaN
+    gd = inside ? gd : 0.f;
+  } else if (!inside) {
+    return make_float4(0.f, 0.f, 0.f, 0.f);
+  }
   const float U2 = r.uni * r.uni;
-  const float gI = gd * (1.f / r.uni + r.inter / U2);
-  const float gA1 = gd * (-r.inter / U2);
-  const float gD = gd * (-1.f / r.odiag);
-  const float gO = gd * (r.diag / (r.odiag * r.odiag));
+  float gI = gd * (1.f / r.uni + r.inter / U2);
+  float gA1 = gd * (-r.inter / U2);
   const Box4 b = r.b;
   float gx1 = 0.f, gy1 = 0.f, gx2 = 0.f, gy2 = 0.f;
+  float gow = 0.f, goh = 0.f;   // gradient of the clamped outer extents' raw values
+  if (kKind == kBoxGiou) {
+    // -(C - U)/C = U/C - 1: d/dU = 1/C (U = area1 + area2 - I), d/dC = -U/C^2
+    const float gU = gd * (1.f / r.carea);
+    gA1 += gU;
+    gI -= gU;
+    const float gC = gd * (-r.uni / (r.carea * r.carea));
+    gow = r.owr >= 0.f ? gC * r.oh : 0.f;
+    goh = r.ohr >= 0.f ? gC * r.ow : 0.f;
+  }
   // area1 = w1*h1
   gx2 += gA1 * r.h1; gx1 -= gA1 * r.h1;
   gy2 += gA1 * r.w1; gy1 -= gA1 * r.w1;
@@ -326,25 +382,95 @@ __device__ __forceinline__ float4 diou_grad(const float4 l, const float4 p, cons
   const float gih = r.ihr >= 0.f ? gI * r.iw : 0.f;
   gx2 += giw * pick_lo(b.x2, t.z); gx1 -= giw * pick_hi(b.x1, t.x);
   gy2 += gih * pick_lo(b.y2, t.w); gy1 -= gih * pick_hi(b.y1, t.y);
-  // diag = (c2 - c1)^2, c1 = (x2 + x1)/2
-  const float gcx1 = gD * -2.f * r.dcx, gcy1 = gD * -2.f * r.dcy;
-  gx1 += gcx1 * .5f; gx2 += gcx1 * .5f;
-  gy1 += gcy1 * .5f; gy2 += gcy1 * .5f;
-  // odiag = clamp(ow)^2 + clamp(oh)^2; ow = max(x2,tx2) - min(x1,tx1)
-  const float gow = r.owr >= 0.f ? gO * 2.f * r.ow : 0.f;
-  const float goh = r.ohr >= 0.f ? gO * 2.f * r.oh : 0.f;
-  gx2 += gow * pick_hi(b.x2, t.z); gx1 -= gow * pick_lo(b.x1, t.x);
-  gy2 += goh * pick_hi(b.y2, t.w); gy1 -= goh * pick_lo(b.y1, t.y);
-  // decode: x1 = cx - W/2, x2 = x1 + W; cx = px + l0*v0*pw, W = pw*exp(l2*v1)
+  if (kKind == kBoxDiou || kKind == kBoxCiou) {
+    const float gD = gd * (-1.f / r.odiag);
+    const float gO = gd * (r.diag / (r.odiag * r.odiag));
+    // diag = (c2 - c1)^2, c1 = (x2 + x1)/2
+    const float gcx1 = gD * -2.f * r.dcx, gcy1 = gD * -2.f * r.dcy;
+    gx1 += gcx1 * .5f; gx2 += gcx1 * .5f;
+    gy1 += gcy1 * .5f; gy2 += gcy1 * .5f;
+    // odiag = clamp(ow)^2 + clamp(oh)^2; ow = max(x2,tx2) - min(x1,tx1)
+    gow = r.owr >= 0.f ? gO * 2.f * r.ow : 0.f;
+    goh = r.ohr >= 0.f ? gO * 2.f * r.oh : 0.f;
+  }
+  if (kKind != kBoxIou) {
+    gx2 += gow * pick_hi(b.x2, t.z); gx1 -= gow * pick_lo(b.x1, t.x);
+    gy2 += goh * pick_hi(b.y2, t.w); gy1 -= goh * pick_lo(b.y1, t.y);
+  }
+  if (kKind == kBoxCiou) {
+    // -a*v, v = 4/pi^2 dat^2, dat = atan(w2/h2) - atan(q), q = w1/h1
+    const float gv = gd * -r.alpha;
+    const float gat1 = gv * (0.40528473456935116f * 2.f * r.dat) * -1.f;
+    const float q = r.w1 / r.h1;
+    const float gq = gat1 / (1.f + q * q);
+    const float gw1 = gq / r.h1, gh1 = gq * (-r.w1 / (r.h1 * r.h1));
+    gx2 += gw1; gx1 -= gw1;
+    gy2 += gh1; gy1 -= gh1;
+  }
+  return make_float4(gx1, gy1, gx2, gy2);
+}
+
+// decode's chain: x1 = cx - W/2, x2 = x1 + W; cx = px + l0*v0*pw, W = pw*exp(l2*v1)
+__device__ __forceinline__ float4 decode_grad(const float4 gb, const float4 l, const float4 p,
+                                              float v0, float v1) {
+  const float gx1 = gb.x, gy1 = gb.y, gx2 = gb.z, gy2 = gb.w;
   const float gcx = gx1 + gx2, gcy = gy1 + gy2;
   const float gW = (gx2 - gx1) * .5f, gH = (gy2 - gy1) * .5f;
   const float W = p.z * expf(l.z * v1);
   const float H = p.w * expf(l.w * v1);
+  float4 g;
   g.x = gcx * v0 * p.z;
   g.y = gcy * v0 * p.w;
   g.z = gW * W * v1;
   g.w = gH * H * v1;
   return g;
+}
+
+// d(loss)/d(loc) for one positive, scaled by s (= dL/dloss_l / N).
+template <int kKind>
+__device__ __forceinline__ float4 iou_grad(const float4 l, const float4 p, const float4 t,
+                                           float v0, float v1, float s) {
+  const IouTerms r = iou_terms<kKind>(decode_box(l, p, v0, v1), t);
+  return decode_grad(iou_box_grad<kKind>(r, t, -s), l, p, v0, v1);
+}
+
+// The stand-alone paired op (IouLoss / bbox_overlaps_* outside the fused loss):
+// one row per thread, float4 in and out, no atomics.  pri == NULL: pred holds
+// corner boxes; otherwise loc offsets decoded against pri[i].
+template <int kKind>
+__global__ void iou_rows_fwd_kernel(const float4* __restrict__ pred,
+                                    const float4* __restrict__ pri,
+                                    const float4* __restrict__ truth, int64_t n, float v0,
+                                    float v1, float* __restrict__ val) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 l = pred[i];
+  Box4 b;
+  if (pri) {
+    b = decode_box(l, pri[i], v0, v1);
+  } else {
+    b.x1 = l.x; b.y1 = l.y; b.x2 = l.z; b.y2 = l.w;
+  }
+  val[i] = iou_clamp<kKind>(iou_terms<kKind>(b, truth[i]).d);
+}
+
+template <int kKind>
+__global__ void iou_rows_bwd_kernel(const float4* __restrict__ pred,
+                                    const float4* __restrict__ pri,
+                                    const float4* __restrict__ truth, int64_t n, float v0,
+                                    float v1, const float* __restrict__ gval,
+                                    float4* __restrict__ gpred) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 l = pred[i], t = truth[i];
+  Box4 b;
+  if (pri) {
+    b = decode_box(l, pri[i], v0, v1);
+  } else {
+    b.x1 = l.x; b.y1 = l.y; b.x2 = l.z; b.y2 = l.w;
+  }
+  const float4 gb = iou_box_grad<kKind>(iou_terms<kKind>(b, t), t, gval[i]);
+  gpred[i] = pri ? decode_grad(gb, l, pri[i], v0, v1) : gb;
 }
 
 // Global max of conf (log_sum_exp uses x.data.max(), :86-88): block partials.
@@ -369,9 +495,10 @@ __global__ __launch_bounds__(kLossBlock) void conf_max_partial(const float* __re
 
 // Per prior: box/landmark smooth-L1 partials, positive counts, and the
 // hard-negative mining loss (lse(x) - x[t], positives zeroed, :256-262).
-// kDiou: the box term is the DIoU loss of the decoded prediction against the
-// raw matched truth (retinaface_training_DIOU.py:600-602); pri/v0/v1 unused otherwise.
-template <bool kDiou>
+// kBox >= 0: the box term is that IoU-family loss of the decoded prediction
+// against the raw matched truth (retinaface_training_DIOU.py:600-602);
+// kBoxSmoothL1: the base loss's, pri/v0/v1 unused.
+template <int kBox>
 __global__ __launch_bounds__(kLossBlock) void loss_elem_kernel(
     const float* __restrict__ loc, const float* __restrict__ conf,
     const float* __restrict__ landm, const float* __restrict__ loc_t,
@@ -402,8 +529,8 @@ __global__ __launch_bounds__(kLossBlock) void loss_elem_kernel(
     if (pos) {
       float4 x = reinterpret_cast<const float4*>(loc)[i];
       float4 y = reinterpret_cast<const float4*>(loc_t)[i];
-      if (kDiou)
-        sl = diou_loss(x, pri[a], y, v0, v1);
+      if constexpr (kBox != kBoxSmoothL1)
+        sl = iou_loss<kBox>(x, pri[a], y, v0, v1);
       else
         sl = smooth_l1(x.x - y.x) + smooth_l1(x.y - y.y) + smooth_l1(x.z - y.z) +
              smooth_l1(x.w - y.w);
@@ -584,7 +711,7 @@ __global__ void loss_normalize_kernel(const float* __restrict__ sums,
 
 __device__ __forceinline__ float sl1_grad(float d) { return d < -1.f ? -1.f : (d > 1.f ? 1.f : d); }
 
-template <bool kDiou>
+template <int kBox>
 __global__ void loss_bwd_kernel(const float* __restrict__ loc, const float* __restrict__ conf,
                                 const float* __restrict__ landm, const float* __restrict__ loc_t,
                                 const int64_t* __restrict__ conf_t,
@@ -606,8 +733,8 @@ __global__ void loss_bwd_kernel(const float* __restrict__ loc, const float* __re
     if (pos) {
       float4 x = reinterpret_cast<const float4*>(loc)[i];
       float4 y = reinterpret_cast<const float4*>(loc_t)[i];
-      if (kDiou)
-        g = diou_grad(x, pri[i % A], y, v0, v1, sl);
+      if constexpr (kBox != kBoxSmoothL1)
+        g = iou_grad<kBox>(x, pri[i % A], y, v0, v1, sl);
       else
         g = make_float4(sl1_grad(x.x - y.x) * sl, sl1_grad(x.y - y.y) * sl,
                         sl1_grad(x.z - y.z) * sl, sl1_grad(x.w - y.w) * sl);
@@ -944,7 +1071,8 @@ extern "C" int jabd_multibox_workspace_size(int64_t batch, int64_t num_priors, s
   return JABD_OK;
 }
 
-static int loss_fwd_impl(const float* loc, const float* conf, const float* landm,
+// kind: kBoxSmoothL1 (priors unused) or one of the four IoU-family kinds.
+static int loss_fwd_impl(int kind, const float* loc, const float* conf, const float* landm,
                          const float* loc_t, const int64_t* conf_t, const float* landm_t,
                          const float* priors, float v0, float v1, int64_t batch,
                          int64_t num_priors, int neg_pos, float* sums, int64_t* counts,
@@ -977,14 +1105,18 @@ static int loss_fwd_impl(const float* loc, const float* conf, const float* landm
   if (int e = check_launch("conf_max")) return e;
   dim3 g((unsigned)nblk, (unsigned)B);
   const float4* pri = reinterpret_cast<const float4*>(priors);
-  if (pri)
-    loss_elem_kernel<true><<<g, kLossBlock, 0, st>>>(loc, conf, landm, loc_t, conf_t, landm_t, A,
-                                                     pri, v0, v1, gpart, (int)ng, mining, sel,
-                                                     part_l, part_lm, npos, npos1);
-  else
-    loss_elem_kernel<false><<<g, kLossBlock, 0, st>>>(loc, conf, landm, loc_t, conf_t, landm_t,
-                                                      A, pri, v0, v1, gpart, (int)ng, mining,
-                                                      sel, part_l, part_lm, npos, npos1);
+#define JABD_LOSS_ELEM(K)                                                                    \
+  loss_elem_kernel<K><<<g, kLossBlock, 0, st>>>(loc, conf, landm, loc_t, conf_t, landm_t, A, \
+                                                pri, v0, v1, gpart, (int)ng, mining, sel,    \
+                                                part_l, part_lm, npos, npos1)
+  switch (kind) {
+    case kBoxIou: JABD_LOSS_ELEM(kBoxIou); break;
+    case kBoxGiou: JABD_LOSS_ELEM(kBoxGiou); break;
+    case kBoxDiou: JABD_LOSS_ELEM(kBoxDiou); break;
+    case kBoxCiou: JABD_LOSS_ELEM(kBoxCiou); break;
+    default: JABD_LOSS_ELEM(kBoxSmoothL1); break;
+  }
+#undef JABD_LOSS_ELEM
   if (int e = check_launch("loss_elem")) return e;
   ohem_select_kernel<<<(unsigned)B, kSelBlock, 0, st>>>(mining, conf, A, neg_pos, npos, sel, ce);
   if (int e = check_launch("ohem_select")) return e;
@@ -999,7 +1131,22 @@ extern "C" int jabd_multibox_loss_fwd_f32(const float* loc, const float* conf,
                                           int64_t batch, int64_t num_priors, int neg_pos,
                                           float* sums, int64_t* counts, uint8_t* sel, void* ws,
                                           size_t ws_bytes, jabd_stream_t stream) {
-  return loss_fwd_impl(loc, conf, landm, loc_t, conf_t, landm_t, nullptr, 0.f, 0.f, batch,
+  return loss_fwd_impl(kBoxSmoothL1, loc, conf, landm, loc_t, conf_t, landm_t, nullptr, 0.f, 0.f,
+                       batch, num_priors, neg_pos, sums, counts, sel, ws, ws_bytes, stream);
+}
+
+extern "C" int jabd_multibox_iou_loss_fwd_f32(const float* loc, const float* conf,
+                                              const float* landm, const float* loc_t,
+                                              const int64_t* conf_t, const float* landm_t,
+                                              const float* priors, float var0, float var1,
+                                              int64_t batch, int64_t num_priors, int neg_pos,
+                                              float* sums, int64_t* counts, uint8_t* sel,
+                                              void* ws, size_t ws_bytes, int32_t kind,
+                                              jabd_stream_t stream) {
+  JABD_REQUIRE(kind >= kBoxIou && kind <= kBoxCiou,
+               "multibox_iou: kind %d (0 Iou, 1 Giou, 2 Diou, 3 Ciou)", kind);
+  JABD_REQUIRE(priors, "multibox_iou: null priors");
+  return loss_fwd_impl(kind, loc, conf, landm, loc_t, conf_t, landm_t, priors, var0, var1, batch,
                        num_priors, neg_pos, sums, counts, sel, ws, ws_bytes, stream);
 }
 
@@ -1011,9 +1158,9 @@ extern "C" int jabd_multibox_diou_loss_fwd_f32(const float* loc, const float* co
                                                float* sums, int64_t* counts, uint8_t* sel,
                                                void* ws, size_t ws_bytes,
                                                jabd_stream_t stream) {
-  JABD_REQUIRE(priors, "multibox_diou: null priors");
-  return loss_fwd_impl(loc, conf, landm, loc_t, conf_t, landm_t, priors, var0, var1, batch,
-                       num_priors, neg_pos, sums, counts, sel, ws, ws_bytes, stream);
+  return jabd_multibox_iou_loss_fwd_f32(loc, conf, landm, loc_t, conf_t, landm_t, priors, var0,
+                                        var1, batch, num_priors, neg_pos, sums, counts, sel, ws,
+                                        ws_bytes, kBoxDiou, stream);
 }
 
 extern "C" int jabd_multibox_loss_finalize_f32(const float* sums, const int64_t* counts,
@@ -1034,10 +1181,41 @@ extern "C" int jabd_multibox_loss_bwd_f32(const float* loc, const float* conf,
   const int64_t total = batch * num_priors;
   if (total <= 0) return JABD_OK;
   JABD_REQUIRE(sel && gout && counts, "multibox_bwd: null pointer");
-  loss_bwd_kernel<false><<<(unsigned)cdiv(total, 256), 256, 0, as_stream(stream)>>>(
+  loss_bwd_kernel<kBoxSmoothL1><<<(unsigned)cdiv(total, 256), 256, 0, as_stream(stream)>>>(
       loc, conf, landm, loc_t, conf_t, landm_t, nullptr, num_priors, 0.f, 0.f, sel, total, gout,
       counts, grad_loc, grad_conf, grad_landm);
   return check_launch("multibox_bwd");
+}
+
+extern "C" int jabd_multibox_iou_loss_bwd_f32(const float* loc, const float* conf,
+                                              const float* landm, const float* loc_t,
+                                              const int64_t* conf_t, const float* landm_t,
+                                              const float* priors, float var0, float var1,
+                                              const uint8_t* sel, int64_t batch,
+                                              int64_t num_priors, const float* gout,
+                                              const int64_t* counts, float* grad_loc,
+                                              float* grad_conf, float* grad_landm, int32_t kind,
+                                              jabd_stream_t stream) {
+  JABD_REQUIRE(kind >= kBoxIou && kind <= kBoxCiou,
+               "multibox_iou_bwd: kind %d (0 Iou, 1 Giou, 2 Diou, 3 Ciou)", kind);
+  const int64_t total = batch * num_priors;
+  if (total <= 0) return JABD_OK;
+  JABD_REQUIRE(sel && gout && counts && priors, "multibox_iou_bwd: null pointer");
+  const float4* pri = reinterpret_cast<const float4*>(priors);
+  const unsigned grid = (unsigned)cdiv(total, 256);
+  hipStream_t st = as_stream(stream);
+#define JABD_LOSS_BWD(K)                                                                      \
+  loss_bwd_kernel<K><<<grid, 256, 0, st>>>(loc, conf, landm, loc_t, conf_t, landm_t, pri,     \
+                                           num_priors, var0, var1, sel, total, gout, counts, \
+                                           grad_loc, grad_conf, grad_landm)
+  switch (kind) {
+    case kBoxIou: JABD_LOSS_BWD(kBoxIou); break;
+    case kBoxGiou: JABD_LOSS_BWD(kBoxGiou); break;
+    case kBoxDiou: JABD_LOSS_BWD(kBoxDiou); break;
+    default: JABD_LOSS_BWD(kBoxCiou); break;
+  }
+#undef JABD_LOSS_BWD
+  return check_launch("multibox_iou_bwd", kind);
 }
 
 extern "C" int jabd_multibox_diou_loss_bwd_f32(const float* loc, const float* conf,
@@ -1049,11 +1227,60 @@ extern "C" int jabd_multibox_diou_loss_bwd_f32(const float* loc, const float* co
                                                const int64_t* counts, float* grad_loc,
                                                float* grad_conf, float* grad_landm,
                                                jabd_stream_t stream) {
-  const int64_t total = batch * num_priors;
-  if (total <= 0) return JABD_OK;
-  JABD_REQUIRE(sel && gout && counts && priors, "multibox_diou_bwd: null pointer");
-  loss_bwd_kernel<true><<<(unsigned)cdiv(total, 256), 256, 0, as_stream(stream)>>>(
-      loc, conf, landm, loc_t, conf_t, landm_t, reinterpret_cast<const float4*>(priors),
-      num_priors, var0, var1, sel, total, gout, counts, grad_loc, grad_conf, grad_landm);
-  return check_launch("multibox_diou_bwd");
+  return jabd_multibox_iou_loss_bwd_f32(loc, conf, landm, loc_t, conf_t, landm_t, priors, var0,
+                                        var1, sel, batch, num_priors, gout, counts, grad_loc,
+                                        grad_conf, grad_landm, kBoxDiou, stream);
+}
+
+// The stand-alone paired overlaps (IouLoss, bbox_overlaps_*): val[i] = the
+// clamped kind-overlap of row i; the backward maps dL/dval to dL/dpred.
+extern "C" int jabd_iou_rows_fwd_f32(const float* pred, const float* priors, const float* truth,
+                                     int64_t n, float var0, float var1, int32_t kind, float* val,
+                                     jabd_stream_t stream) {
+  JABD_REQUIRE(kind >= kBoxIou && kind <= kBoxCiou,
+               "iou_rows: kind %d (0 Iou, 1 Giou, 2 Diou, 3 Ciou)", kind);
+  JABD_REQUIRE(n >= 0, "iou_rows: n = %lld", (long long)n);
+  if (n == 0) return JABD_OK;
+  JABD_REQUIRE(pred && truth && val, "iou_rows: null pointer");
+  const float4* p4 = reinterpret_cast<const float4*>(pred);
+  const float4* pri = reinterpret_cast<const float4*>(priors);
+  const float4* t4 = reinterpret_cast<const float4*>(truth);
+  const unsigned grid = (unsigned)cdiv(n, 256);
+  hipStream_t st = as_stream(stream);
+#define JABD_ROWS_FWD(K) \
+  iou_rows_fwd_kernel<K><<<grid, 256, 0, st>>>(p4, pri, t4, n, var0, var1, val)
+  switch (kind) {
+    case kBoxIou: JABD_ROWS_FWD(kBoxIou); break;
+    case kBoxGiou: JABD_ROWS_FWD(kBoxGiou); break;
+    case kBoxDiou: JABD_ROWS_FWD(kBoxDiou); break;
+    default: JABD_ROWS_FWD(kBoxCiou); break;
+  }
+#undef JABD_ROWS_FWD
+  return check_launch("iou_rows_fwd", kind);
+}
+
+extern "C" int jabd_iou_rows_bwd_f32(const float* pred, const float* priors, const float* truth,
+                                     int64_t n, float var0, float var1, int32_t kind,
+                                     const float* gval, float* gpred, jabd_stream_t stream) {
+  JABD_REQUIRE(kind >= kBoxIou && kind <= kBoxCiou,
+               "iou_rows_bwd: kind %d (0 Iou, 1 Giou, 2 Diou, 3 Ciou)", kind);
+  JABD_REQUIRE(n >= 0, "iou_rows_bwd: n = %lld", (long long)n);
+  if (n == 0) return JABD_OK;
+  JABD_REQUIRE(pred && truth && gval && gpred, "iou_rows_bwd: null pointer");
+  const float4* p4 = reinterpret_cast<const float4*>(pred);
+  const float4* pri = reinterpret_cast<const float4*>(priors);
+  const float4* t4 = reinterpret_cast<const float4*>(truth);
+  float4* g4 = reinterpret_cast<float4*>(gpred);
+  const unsigned grid = (unsigned)cdiv(n, 256);
+  hipStream_t st = as_stream(stream);
+#define JABD_ROWS_BWD(K) \
+  iou_rows_bwd_kernel<K><<<grid, 256, 0, st>>>(p4, pri, t4, n, var0, var1, gval, g4)
+  switch (kind) {
+    case kBoxIou: JABD_ROWS_BWD(kBoxIou); break;
+    case kBoxGiou: JABD_ROWS_BWD(kBoxGiou); break;
+    case kBoxDiou: JABD_ROWS_BWD(kBoxDiou); break;
+    default: JABD_ROWS_BWD(kBoxCiou); break;
+  }
+#undef JABD_ROWS_BWD
+  return check_launch("iou_rows_bwd", kind);
 }

@@ -180,6 +180,14 @@ SIGNATURES = {
                                         c_vp],
     "jabd_multibox_diou_loss_bwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32,
                                         c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "jabd_multibox_iou_loss_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32,
+                                       c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_size,
+                                       c_i32, c_vp],   # ..., kind, stream
+    "jabd_multibox_iou_loss_bwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32,
+                                       c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                       c_vp],
+    "jabd_iou_rows_fwd_f32": [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_i32, c_vp, c_vp],
+    "jabd_iou_rows_bwd_f32": [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp],
     "jabd_conv_pack_tn": [c_int],
     "jabd_conv_pack_tn32": [c_int],
     "jabd_conv2d_nhwc_f32": [ctypes.POINTER(ConvArgs), c_vp],

@@ -239,11 +239,31 @@ def match_encode(targets, priors, threshold, variances, raw_loc=False):
 
 
 # --------------------------------------------------------------------------- loss
+IOU_KINDS = {"Iou": 0, "Giou": 1, "Diou": 2, "Ciou": 3}
+
+
+def iou_kind(kind):
+    """The C-ABI kind (0..3) of an IouLoss losstype: one of the exact names
+    'Iou', 'Giou', 'Diou', 'Ciou' (nets/retinaface_training_DIOU.py:507-516), or
+    that integer.  The reference treats every other string as CIoU; here it
+    is an error."""
+    if isinstance(kind, str):
+        if kind not in IOU_KINDS:
+            raise ValueError(f"losstype must be one of {', '.join(IOU_KINDS)}; got {kind!r}")
+        return IOU_KINDS[kind]
+    if isinstance(kind, bool) or not isinstance(kind, int) or not 0 <= kind <= 3:
+        raise ValueError(f"losstype must be one of {', '.join(IOU_KINDS)} (or 0..3); "
+                         f"got {kind!r}")
+    return kind
+
+
 def multibox_sums(loc, conf, landm, loc_t, conf_t, landm_t, neg_pos, diou=None):
     """Un-normalised MultiBoxLoss sums [3], counts [2] and the selection mask.
 
-    diou=(priors [A,4], variances): the box term is the DIoU loss of
-    nets/retinaface_training_DIOU.py:491-522 (loc_t from match_encode(raw_loc=True)).
+    diou=(priors [A,4], variances) or (priors, variances, kind): the box term is
+    the IouLoss of nets/retinaface_training_DIOU.py:491-522 (loc_t from
+    match_encode(raw_loc=True)); kind is a losstype name or 0..3 (iou_kind),
+    'Diou' when left out.
     """
     loc, conf, landm = (_dev("loss.loc", loc), _dev("loss.conf", conf),
                         _dev("loss.landm", landm))
@@ -251,6 +271,8 @@ def multibox_sums(loc, conf, landm, loc_t, conf_t, landm_t, neg_pos, diou=None):
     conf_t = _dev("loss.conf_t", conf_t, torch.int64)
     B, A = loc.shape[0], loc.shape[1]
     dev = loc.device
+    if diou is not None:
+        pri, var, kind = _iou_priors(diou, A)
     sums = torch.empty(3, dtype=torch.float32, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     sel = torch.empty((B, A), dtype=torch.uint8, device=dev)
@@ -260,19 +282,19 @@ def multibox_sums(loc, conf, landm, loc_t, conf_t, landm_t, neg_pos, diou=None):
              _p(landm_t), B, A, int(neg_pos), _p(sums), _p(counts), _p(sel), _p(ws),
              ws.numel(), _stream())
     else:
-        pri, var = _diou_priors(diou, A)
-        call("jabd_multibox_diou_loss_fwd_f32", _p(loc), _p(conf), _p(landm), _p(loc_t),
+        call("jabd_multibox_iou_loss_fwd_f32", _p(loc), _p(conf), _p(landm), _p(loc_t),
              _p(conf_t), _p(landm_t), _p(pri), float(var[0]), float(var[1]), B, A,
-             int(neg_pos), _p(sums), _p(counts), _p(sel), _p(ws), ws.numel(), _stream())
+             int(neg_pos), _p(sums), _p(counts), _p(sel), _p(ws), ws.numel(), kind, _stream())
     return sums, counts, sel
 
 
-def _diou_priors(diou, A):
-    pri, var = diou
+def _iou_priors(diou, A):
+    pri, var = diou[0], diou[1]
+    kind = iou_kind(diou[2]) if len(diou) > 2 else IOU_KINDS["Diou"]
     pri = _dev("loss.priors", pri)
     if tuple(pri.shape) != (A, 4):
-        raise ValueError(f"DIoU loss: priors {tuple(pri.shape)} != ({A}, 4)")
-    return pri, var
+        raise ValueError(f"IoU loss: priors {tuple(pri.shape)} != ({A}, 4)")
+    return pri, var, kind
 
 
 def multibox_normalize(sums, counts):
@@ -282,7 +304,10 @@ def multibox_normalize(sums, counts):
 
 
 def multibox_backward(loc, conf, landm, loc_t, conf_t, landm_t, sel, gout, counts, diou=None):
+    """The three gradients; diou as multibox_sums takes it."""
     B, A = loc.shape[0], loc.shape[1]
+    if diou is not None:
+        pri, var, kind = _iou_priors(diou, A)
     gl = torch.empty_like(loc)
     gc = torch.empty_like(conf)
     glm = torch.empty_like(landm)
@@ -292,11 +317,62 @@ def multibox_backward(loc, conf, landm, loc_t, conf_t, landm_t, sel, gout, count
              _p(landm_t), _p(sel), B, A, _p(gout), _p(counts), _p(gl), _p(gc), _p(glm),
              _stream())
     else:
-        pri, var = _diou_priors(diou, A)
-        call("jabd_multibox_diou_loss_bwd_f32", _p(loc), _p(conf), _p(landm), _p(loc_t),
+        call("jabd_multibox_iou_loss_bwd_f32", _p(loc), _p(conf), _p(landm), _p(loc_t),
              _p(conf_t), _p(landm_t), _p(pri), float(var[0]), float(var[1]), _p(sel), B, A,
-             _p(gout), _p(counts), _p(gl), _p(gc), _p(glm), _stream())
+             _p(gout), _p(counts), _p(gl), _p(gc), _p(glm), kind, _stream())
     return gl, gc, glm
+
+
+def _iou_rows_args(pred, priors, truth, kind):
+    pred, truth = _dev("iou_rows.pred", pred), _dev("iou_rows.truth", truth)
+    if pred.dim() != 2 or pred.shape[1] != 4 or truth.dim() != 2 or truth.shape[1] != 4:
+        raise ValueError(f"iou_rows: [P,4] boxes, got {tuple(pred.shape)} and "
+                         f"{tuple(truth.shape)}")
+    if pred.shape[0] != truth.shape[0]:
+        raise ValueError(f"iou_rows: paired rows only ({pred.shape[0]} predictions vs "
+                         f"{truth.shape[0]} truths; the reference's row swap and broadcast "
+                         "are not reproduced)")
+    if priors is not None:
+        priors = _dev("iou_rows.priors", priors)
+        if priors.shape != pred.shape:
+            raise ValueError(f"iou_rows: priors {tuple(priors.shape)} != {tuple(pred.shape)}")
+    return pred, priors, truth, iou_kind(kind)
+
+
+def iou_rows(pred, truth, kind, priors=None, variances=(0.1, 0.2)):
+    """bbox_overlaps_<kind> for paired rows (nets/retinaface_training_DIOU.py:
+    339-490): the clamped overlaps [P] of pred [P,4] against truth [P,4].
+    priors=None: pred holds corner boxes; otherwise loc offsets decoded in the
+    kernel against priors [P,4] with `variances` (IouLoss pred_mode 'Center').
+    P == 0 launches nothing."""
+    pred, priors, truth, k = _iou_rows_args(pred, priors, truth, kind)
+    val = torch.empty(pred.shape[0], dtype=torch.float32, device=pred.device)
+    call("jabd_iou_rows_fwd_f32", _p(pred), _p(priors), _p(truth), pred.shape[0],
+         float(variances[0]), float(variances[1]), k, _p(val), _stream())
+    return val
+
+
+def iou_rows_backward(pred, truth, kind, gval, priors=None, variances=(0.1, 0.2)):
+    """dL/dpred [P,4] of iou_rows given dL/dval [P]."""
+    pred, priors, truth, k = _iou_rows_args(pred, priors, truth, kind)
+    gval = _dev("iou_rows.gval", gval)
+    if gval.shape != pred.shape[:1]:
+        raise ValueError(f"iou_rows: gval {tuple(gval.shape)} != ({pred.shape[0]},)")
+    gpred = torch.empty_like(pred)
+    call("jabd_iou_rows_bwd_f32", _p(pred), _p(priors), _p(truth), pred.shape[0],
+         float(variances[0]), float(variances[1]), k, _p(gval), _p(gpred), _stream())
+    return gpred
+
+
+def fixed_sum(x):
+    """Σ x of a device float32 vector as a [1] tensor, in a fixed order
+    (jabd_colsum_f32): two runs agree bit for bit.  Empty -> 0."""
+    x = _dev("fixed_sum.x", x).reshape(-1)
+    if x.numel() == 0:
+        return torch.zeros(1, dtype=torch.float32, device=x.device)
+    out = torch.empty(1, dtype=torch.float32, device=x.device)
+    call("jabd_colsum_f32", _p(x), x.numel(), 1, _p(out), _stream())
+    return out
 
 
 # --------------------------------------------------------------------------- letterbox

@@ -22,6 +22,8 @@ from jabd_amd.functional import window_copies
 class _MultiBoxLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, loc, conf, landm, loc_t, conf_t, landm_t, neg_pos, group, diou=None):
+        # diou: None, or (priors, variances[, kind]) — the IoU-family box term and
+        # its kind (ops.multibox_sums), carried to the backward unchanged
         sums, counts, sel = ops.multibox_sums(loc, conf, landm, loc_t, conf_t, landm_t, neg_pos,
                                               diou)
         if group is not None:  # (process group,) — see MultiBoxLoss.global_counts
