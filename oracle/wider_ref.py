@@ -2,7 +2,8 @@
 :255-287 (image_eval), :290-305 (img_pr_info) restated in numpy float64, summed
 over images as evaluation() does (:347-375).  The reference ships no WIDER
 ground truth or prediction files, so this is pinned by the hand-derived cases
-in tests/test_wider_eval.py."""
+in tests/test_wider_eval.py and tests/test_wider_eval_edges.py (argmax ties,
+IoU == threshold, score == threshold, NaN overlaps, unsorted scores)."""
 import numpy as np
 
 

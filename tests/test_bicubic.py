@@ -3,7 +3,9 @@
 align_corners=True)) on the device vs PyTorch-CPU fp32 — the reference's own
 op.  Tolerances: forward 1e-5 relative to the max magnitude (fp32 ulp-level
 reordering), backward 1e-5 (summation order); the backward is a gather
-(no atomics) and bit-reproducible run to run."""
+(no atomics) and bit-reproducible run to run.  Every small ratio, the
+down-sampling windows and the reference-free invariants are in
+tests/test_bicubic_edges.py."""
 import pytest
 import torch
 import torch.nn.functional as F

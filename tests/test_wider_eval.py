@@ -1,7 +1,9 @@
 """§8f rank 3: WIDER FACE evaluation core (utils/evaluation.py:255-305 summed
 over images) on the device vs the numpy oracle (oracle/wider_ref.py).  The
-reference ships no WIDER files; the oracle is pinned by the hand cases below.
-GPU parity is exact: the pr curve holds integer counts."""
+reference ships no WIDER files; the oracle is pinned by the hand case below and
+the nine of tests/test_wider_eval_edges.py, which also holds the sets that loop
+the kernel's workgroup more than once.  GPU parity is exact: the pr curve holds
+integer counts."""
 import numpy as np
 import pytest
 
