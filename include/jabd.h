@@ -172,6 +172,76 @@ int jabd_detect_ex_f32(const float* loc, const float* conf, const float* landm,
                        int32_t kind, double beta1, int64_t top_k);
 
 /* ------------------------------------------------------------------------ *
+ * Gaussian Soft-NMS — softer_nms of utils/utils_bbox.py:65-114, batched: B
+ * independent images of up to n rows, one workgroup per image.  Instead of
+ * removing the neighbours of a selected box the rule decays their scores and
+ * drops a row only when its score falls below `prune`.  Per image, on the
+ * candidate rows in input order (N = their number):
+ *   for i = 0, 1, ... while i < N:
+ *     m = first position in [i, N) holding the maximum score (a NaN score
+ *         counts as the maximum, -0 equals +0: numpy.argmax);
+ *     swap rows m and i;
+ *     for pos = i + 1 ... sequentially, N shrinking:
+ *       o = IoU(row i, row pos) in fp32, every operation rounded on its own:
+ *             area  = ((x2 - x1) + offset) * ((y2 - y1) + offset)
+ *             w     = max(0, (min(x2i,x2j) - max(x1i,x1j)) + offset), h likewise
+ *             inter = w * h;   o = inter / ((area_i + area_j) - inter)
+ *       if o > 0 (a NaN overlap — a NaN coordinate, 0/0 — decays nothing):
+ *         score[pos] = (float)((double)score[pos] * exp(-((double)o*(double)o) / sigma))
+ *         if (double)score[pos] < prune: swap rows pos and N-1; N -= 1; stay
+ *   result: rows [0, N) in array order with their decayed scores.
+ * The swaps are part of the contract: they decide the order of the result and
+ * which of two equal scores is selected first.  exp is the library's own
+ * (csrc/softnms_math.h: plain IEEE double arithmetic, error below one ulp),
+ * so a host that compiles that header reproduces every bit.
+ *   boxes, scores, n_valid  as jabd_batched_nms_f32 (strides in floats; scores
+ *          may alias a column of boxes; neither is modified).
+ *   candidates: rows r < n_valid[b] with score >= score_threshold, in
+ *          ascending row order.  A NaN score fails the comparison and is
+ *          dropped; -INFINITY keeps every other row.
+ *   top_k > 0: only the top_k best candidates take part — descending score,
+ *          stable, the lower row first at the cut, as the other kinds choose
+ *          them — still starting in ascending row order.  top_k <= 0: no cut.
+ *   sigma  positive and finite (the reference's 0.5).
+ *   offset finite: 1 for pixel boxes (the reference), 0 for normalised ones.
+ *   prune  finite: the score below which a decayed row is dropped (the
+ *          reference's 0.001).  Only a row decayed in this sweep is tested.
+ *   keep   device int64[B, n]: keep[b, :n_keep[b]] are the original row
+ *          indices in result order; keep_scores device float[B, n]: their
+ *          decayed scores; n_keep device int64[B].
+ * sigma / offset / prune outside these ranges return JABD_EINVAL before any
+ * device work.  batch == 0 launches nothing; n == 0 sets n_keep to 0.  No host
+ * synchronisation and no memset: the call can be captured in a HIP graph.
+ * Cost: O(result rows x candidates) per image on one workgroup.  The state
+ * lives in LDS up to 16000 candidates (bounded by n, or by top_k when it cuts
+ * lower) and in the workspace above; the launch witness names the form
+ * ("soft_nms_lds" tag 1, "soft_nms_ws" tag 2).  n < 2^24.
+ * ------------------------------------------------------------------------ */
+int jabd_soft_nms_workspace_size(int64_t batch, int64_t n, size_t* bytes);
+int jabd_batched_soft_nms_f32(const float* boxes, int64_t box_stride,
+                              int64_t box_bstride, const float* scores,
+                              int64_t score_stride, int64_t score_bstride,
+                              const int64_t* n_valid, int64_t batch, int64_t n,
+                              double sigma, float offset, double prune,
+                              float score_threshold, int64_t top_k,
+                              int64_t* keep, float* keep_scores, int64_t* n_keep,
+                              void* ws, size_t ws_bytes, jabd_stream_t stream);
+
+/* jabd_detect_f32 with the Soft-NMS above in place of the hard rule: decode +
+ * decode_landm + conf[:,1] + score filter (conf_threshold) + Soft-NMS.
+ * out [B, A, 15]: out[b, :n_keep[b]] are the rows in result order with the
+ * decayed score in column 4.  The decoded boxes are normalised, so offset is
+ * normally 0 (with the reference's pixel +1 every pair would overlap).
+ * Workspace: jabd_detect_soft_workspace_size. */
+int jabd_detect_soft_workspace_size(int64_t batch, int64_t num_priors, size_t* bytes);
+int jabd_detect_soft_f32(const float* loc, const float* conf, const float* landm,
+                         const float* priors, int64_t batch, int64_t num_priors,
+                         float var0, float var1, float conf_threshold,
+                         double sigma, float offset, double prune, int64_t top_k,
+                         float* out, int64_t* n_keep, void* ws, size_t ws_bytes,
+                         jabd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * A7/A8 anchor matching + encoding — nets/retinaface_training.py:93-162
  * (match/encode/encode_landm) for a whole batch in one pass.
  *   targets  [T, 15] device fp32: the B per-image target tensors concatenated

@@ -5,6 +5,8 @@
 // reference's separate tensor ops.
 #include <math.h>
 
+#include <cmath>
+
 #include "common.h"
 #include "nms_internal.h"
 
@@ -998,6 +1000,77 @@ extern "C" int jabd_detect_f32(const float* loc, const float* conf, const float*
   return jabd_detect_ex_f32(loc, conf, landm, priors, batch, num_priors, var0, var1,
                             conf_threshold, nms_threshold, out, n_keep, ws, ws_bytes, stream,
                             kNmsIoU, 1.0, 0);
+}
+
+// gather_rows_kernel with column 4 taken from the Soft-NMS's decayed scores
+__global__ void gather_rows_soft_kernel(const float* __restrict__ rows,
+                                        const int64_t* __restrict__ keep,
+                                        const float* __restrict__ keep_scores,
+                                        const int64_t* __restrict__ n_keep, int64_t A,
+                                        float* __restrict__ out) {
+  int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int b = blockIdx.y;
+  if (k >= n_keep[b]) return;
+  int64_t src = keep[(int64_t)b * A + k];
+  const float* r = rows + ((int64_t)b * A + src) * 15;
+  float* o = out + ((int64_t)b * A + k) * 15;
+#pragma unroll
+  for (int c = 0; c < 15; ++c) o[c] = r[c];
+  o[4] = keep_scores[(int64_t)b * A + k];
+}
+
+static size_t detect_soft_ws(int64_t B, int64_t A) {
+  Sizer s;
+  s.take<float>(B * A * 15);
+  s.take<int64_t>(B * A);
+  s.take<float>(B * A);
+  s.take<char>(soft_nms_ws_bytes(B, A));
+  return s.used;
+}
+
+extern "C" int jabd_detect_soft_workspace_size(int64_t batch, int64_t num_priors,
+                                               size_t* bytes) {
+  JABD_REQUIRE(bytes && batch >= 0 && num_priors >= 0, "detect_soft_workspace_size: bad args");
+  *bytes = detect_soft_ws(batch, num_priors);
+  return JABD_OK;
+}
+
+extern "C" int jabd_detect_soft_f32(const float* loc, const float* conf, const float* landm,
+                                    const float* priors, int64_t batch, int64_t num_priors,
+                                    float var0, float var1, float conf_threshold, double sigma,
+                                    float offset, double prune, int64_t top_k, float* out,
+                                    int64_t* n_keep, void* ws, size_t ws_bytes,
+                                    jabd_stream_t stream) {
+  JABD_REQUIRE(batch >= 0 && num_priors >= 0, "detect_soft: negative size");
+  hipStream_t st = as_stream(stream);
+  if (batch == 0 || num_priors == 0)  // the argument checks; n_keep = 0
+    return soft_nms_core(nullptr, 15, 0, nullptr, 15, 0, nullptr, batch, 0, sigma, offset, prune,
+                         conf_threshold, top_k, nullptr, nullptr, n_keep, nullptr, 0, st);
+  JABD_REQUIRE(loc && conf && landm && priors && out && n_keep, "detect_soft: null pointer");
+  JABD_REQUIRE(ws_bytes >= detect_soft_ws(batch, num_priors), "detect_soft: workspace too small");
+  Carve cv(ws, ws_bytes);
+  float* rows = cv.take<float>(batch * num_priors * 15);
+  int64_t* keep = cv.take<int64_t>(batch * num_priors);
+  float* keep_scores = cv.take<float>(batch * num_priors);
+  size_t nws = soft_nms_ws_bytes(batch, num_priors);
+  void* nmsws = cv.take<char>(nws);
+  const int64_t total = batch * num_priors;
+  // the Soft-NMS checks sigma / offset / prune; nothing may launch before it does
+  JABD_REQUIRE(sigma > 0.0 && std::isfinite(sigma) && std::isfinite(offset) &&
+                   std::isfinite(prune),
+               "detect_soft: sigma must be positive and finite, offset and prune finite "
+               "(got %g, %g, %g)", sigma, (double)offset, prune);
+  detect_rows_kernel<<<(unsigned)cdiv(total, 256), 256, 0, st>>>(
+      loc, conf, landm, reinterpret_cast<const float4*>(priors), num_priors, total, var0, var1,
+      rows);
+  if (int e = check_launch("detect_rows")) return e;
+  if (int e = soft_nms_core(rows, 15, num_priors * 15, rows + 4, 15, num_priors * 15, nullptr,
+                            batch, num_priors, sigma, offset, prune, conf_threshold, top_k, keep,
+                            keep_scores, n_keep, nmsws, nws, st))
+    return e;
+  dim3 g((unsigned)cdiv(num_priors, 256), (unsigned)batch);
+  gather_rows_soft_kernel<<<g, 256, 0, st>>>(rows, keep, keep_scores, n_keep, num_priors, out);
+  return check_launch("detect_soft_gather");
 }
 
 static size_t match_ws(int64_t B, int64_t A) {

@@ -14,4 +14,14 @@ int nms_core(const float* boxes, int64_t box_stride, int64_t box_bstride,
              const int64_t* n_valid, int64_t batch, int64_t n, double iou_thr,
              float score_thr, int64_t* keep, int64_t* n_keep, void* ws,
              size_t ws_bytes, hipStream_t st, int kind, double beta1, int64_t top_k);
+
+// Gaussian Soft-NMS (soft_nms.hip; shared with jabd_detect_soft_f32): the
+// arguments of jabd_batched_soft_nms_f32, which also checks them.
+size_t soft_nms_ws_bytes(int64_t batch, int64_t n);
+int soft_nms_core(const float* boxes, int64_t box_stride, int64_t box_bstride,
+                  const float* scores, int64_t score_stride, int64_t score_bstride,
+                  const int64_t* n_valid, int64_t batch, int64_t n, double sigma, float offset,
+                  double prune, float score_thr, int64_t top_k, int64_t* keep,
+                  float* keep_scores, int64_t* n_keep, void* ws, size_t ws_bytes,
+                  hipStream_t st);
 }  // namespace jabd

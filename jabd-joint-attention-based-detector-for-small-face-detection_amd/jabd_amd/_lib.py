@@ -127,6 +127,13 @@ SIGNATURES = {
                         c_vp, c_vp, c_vp, c_size, c_vp],
     "jabd_detect_ex_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f64,
                            c_vp, c_vp, c_vp, c_size, c_vp, c_i32, c_f64, c_i64],
+    "jabd_soft_nms_workspace_size": [c_i64, c_i64, c_sizep],
+    "jabd_batched_soft_nms_f32": [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
+                                  c_f64, c_f32, c_f64, c_f32, c_i64,   # sigma, offset, prune,
+                                  c_vp, c_vp, c_vp, c_vp, c_size, c_vp],  # score thr, top_k
+    "jabd_detect_soft_workspace_size": [c_i64, c_i64, c_sizep],
+    "jabd_detect_soft_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32,
+                             c_f64, c_f32, c_f64, c_i64, c_vp, c_vp, c_vp, c_size, c_vp],
     "jabd_match_workspace_size": [c_i64, c_i64, c_sizep],
     "jabd_match_encode_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_f32, c_f32, c_f32,
                               c_vp, c_vp, c_vp, c_vp, c_size, c_vp],

@@ -166,16 +166,86 @@ def nms(boxes, scores, iou_threshold):
     return keep[0, : int(n_keep[0].item())]
 
 
+# --------------------------------------------------------------------------- Soft-NMS
+_SOFT_KINDS = ("softnms", "softernms")
+SOFT_PRUNE = 0.001   # the reference's literal (utils/utils_bbox.py:104)
+
+
+def is_soft_kind(kind):
+    """True for the Gaussian Soft-NMS names ("softnms", "softernms"): the kind
+    of detect / non_max_suppression / detect_image that runs batched_soft_nms.
+    batched_nms and batched_nms_stats return index lists only and have no such
+    kind (their _kind_code rejects the names)."""
+    return isinstance(kind, str) and kind in _SOFT_KINDS
+
+
+def _soft_args(sigma, offset, prune=SOFT_PRUNE):
+    sigma, offset, prune = float(sigma), float(offset), float(prune)
+    if not (sigma > 0.0 and math.isfinite(sigma)):
+        raise ValueError(f"soft nms: sigma must be positive and finite, got {sigma!r}")
+    if not math.isfinite(offset):
+        raise ValueError(f"soft nms: offset must be finite, got {offset!r}")
+    if not math.isfinite(prune):
+        raise ValueError(f"soft nms: prune must be finite, got {prune!r}")
+    return sigma, offset
+
+
+def batched_soft_nms(boxes, scores, sigma=0.5, offset=1.0, score_threshold=-math.inf,
+                     prune=SOFT_PRUNE, n_valid=None, top_k=0):
+    """Gaussian Soft-NMS per image (the reference's softer_nms, utils/
+    utils_bbox.py:65-114; semantics: jabd_batched_soft_nms_f32 in jabd.h).
+
+    boxes [B,N,4] (or a [B,N,>=5] row tensor whose first 4 columns are boxes),
+    scores [B,N]; neither is modified.  Returns (keep [B,N] int64, keep_scores
+    [B,N] float32, n_keep [B] int64) on the device: keep[b,:n_keep[b]] are the
+    original row indices in the reference's result order (its swaps included)
+    and keep_scores their decayed scores.  A selected box decays every later
+    overlapping score by exp(-IoU^2 / sigma); a decayed score below `prune`
+    drops its row.  offset: the reference's +1 of pixel boxes (pass 0 for
+    normalised boxes).  Candidates: rows < n_valid[b] with score >=
+    score_threshold (NaN scores are dropped); top_k > 0 keeps the top_k best.
+    """
+    sigma, offset = _soft_args(sigma, offset, prune)
+    if boxes.dim() != 3 or boxes.shape[-1] < 4:
+        raise ValueError(f"batched_soft_nms: boxes must be [B,N,>=4], got {tuple(boxes.shape)}")
+    boxes = _dev("soft_nms.boxes", boxes)
+    scores = _dev("soft_nms.scores", scores)
+    B, N = boxes.shape[0], boxes.shape[1]
+    if scores.shape != (B, N):
+        raise ValueError(f"batched_soft_nms: scores {tuple(scores.shape)} != {(B, N)}")
+    dev = boxes.device
+    keep = torch.empty((B, N), dtype=torch.int64, device=dev)
+    keep_scores = torch.empty((B, N), dtype=torch.float32, device=dev)
+    n_keep = torch.zeros((B,), dtype=torch.int64, device=dev)
+    if n_valid is not None:
+        n_valid = _dev("soft_nms.n_valid", n_valid, torch.int64)
+    ws = _ws(_size_query("jabd_soft_nms_workspace_size", B, N), dev)
+    C = boxes.shape[-1]
+    call("jabd_batched_soft_nms_f32", _p(boxes), C, N * C, _p(scores), 1, N, _p(n_valid), B, N,
+         sigma, offset, float(prune), float(score_threshold), int(top_k), _p(keep),
+         _p(keep_scores), _p(n_keep), _p(ws), ws.numel(), _stream())
+    return keep, keep_scores, n_keep
+
+
 def detect(loc, conf, landm, priors, variances, conf_threshold=0.5, nms_threshold=0.3,
-           nms_kind="greedynms", beta1=1.0, top_k=0):
+           nms_kind="greedynms", beta1=1.0, top_k=0, sigma=0.5, soft_offset=0.0):
     """predict.py:162-181 on device for a batch: decode + filter + NMS.
 
     loc [B,A,4], conf [B,A,2] (eval softmax), landm [B,A,10].
     Returns (rows [B,A,15], n_keep [B]); rows[b,:n_keep[b]] are the kept
     detections (x1,y1,x2,y2,score,landmarks) in NMS order.
     nms_kind, beta1, top_k: the suppression rule, as batched_nms.
+    nms_kind "softnms" (or "softernms"): Gaussian Soft-NMS (batched_soft_nms)
+    with `sigma` and `soft_offset`; nms_threshold and beta1 are ignored, the
+    rows are in the Soft-NMS's result order and column 4 holds the decayed
+    score.  soft_offset defaults to 0, not the reference's pixel +1: the
+    decoded boxes are normalised, and with +1 every pair would overlap.
     """
-    k = _kind_code(nms_kind, beta1)
+    soft = is_soft_kind(nms_kind)
+    if soft:
+        sigma, soft_offset = _soft_args(sigma, soft_offset)
+    else:
+        k = _kind_code(nms_kind, beta1)
     loc = _dev("detect.loc", loc)
     conf = _dev("detect.conf", conf)
     landm = _dev("detect.landm", landm)
@@ -186,6 +256,12 @@ def detect(loc, conf, landm, priors, variances, conf_threshold=0.5, nms_threshol
     dev = loc.device
     out = torch.empty((B, A, 15), dtype=torch.float32, device=dev)
     n_keep = torch.empty((B,), dtype=torch.int64, device=dev)   # written by every call
+    if soft:
+        ws = _ws(_size_query("jabd_detect_soft_workspace_size", B, A), dev)
+        call("jabd_detect_soft_f32", _p(loc), _p(conf), _p(landm), _p(priors), B, A,
+             float(variances[0]), float(variances[1]), float(conf_threshold), sigma, soft_offset,
+             SOFT_PRUNE, int(top_k), _p(out), _p(n_keep), _p(ws), ws.numel(), _stream())
+        return out, n_keep
     ws = _ws(_size_query("jabd_detect_workspace_size", B, A), dev)
     args = (_p(loc), _p(conf), _p(landm), _p(priors), B, A,
             float(variances[0]), float(variances[1]), float(conf_threshold), float(nms_threshold),

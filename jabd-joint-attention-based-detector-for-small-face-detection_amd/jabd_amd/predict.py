@@ -36,12 +36,13 @@ class GraphedDetect:
     changed (hipmodule generation)."""
 
     def __init__(self, net, shape, priors, variances, conf_thres, nms_thres, device,
-                 nms_kind="greedynms", beta1=1.0, top_k=0):
+                 nms_kind="greedynms", beta1=1.0, top_k=0, sigma=0.5, soft_offset=0.0):
         self.net, self.gen = net, hipmodule.generation()
         self.x = torch.zeros(shape, dtype=torch.float32, device=device)
         self.pri = priors
         self.args = (variances, conf_thres, nms_thres)
         self.rule = (nms_kind, float(beta1), int(top_k))
+        self.soft = (float(sigma), float(soft_offset))   # read by the "softnms" kind only
         cur = torch.cuda.current_stream(device)
         side = torch.cuda.Stream(device=device)
         side.wait_stream(cur)
@@ -58,8 +59,9 @@ class GraphedDetect:
             loc, conf, landm = self.net(self.x)
             v, ct, nt = self.args
             kind, beta1, top_k = self.rule
+            sigma, soft_offset = self.soft
             return ops.detect(loc, conf, landm, self.pri, v, ct, nt, nms_kind=kind, beta1=beta1,
-                              top_k=top_k)
+                              top_k=top_k, sigma=sigma, soft_offset=soft_offset)
 
     def __call__(self, x):
         self.x.copy_(x)
@@ -68,15 +70,23 @@ class GraphedDetect:
 
 
 def graphed_detect(net, x, priors, variances, conf_thres=0.5, nms_thres=0.3,
-                   nms_kind="greedynms", beta1=1.0, top_k=0):
+                   nms_kind="greedynms", beta1=1.0, top_k=0, sigma=0.5, soft_offset=0.0):
     """ops.detect(*net(x), ...) for a batch of the shape of x, through a HIP
     graph cached on the module per (shape, device, thresholds, priors,
     suppression rule); rebuilt when the module's eval packs may have changed.
-    The rule (kind, beta1, top_k) is baked into the captured launches, so it
-    is part of the key: a graph captured for one rule never serves another."""
-    code = ops._kind_code(nms_kind, beta1)
-    # the IoU kind ignores beta1: one graph whatever value came with it
-    rule = (code, float(beta1) if code else 1.0, max(int(top_k), 0))
+    The rule (kind, beta1, top_k; for "softnms": sigma, soft_offset, top_k) is
+    baked into the captured launches, so it is part of the key: a graph
+    captured for one rule never serves another."""
+    soft = ops.is_soft_kind(nms_kind)
+    if soft:
+        # the Soft-NMS ignores nms_thres and beta1: one graph whatever came with them
+        sigma, soft_offset = ops._soft_args(sigma, soft_offset)
+        rule = ("soft", sigma, soft_offset, max(int(top_k), 0))
+        nms_thres = 0.0
+    else:
+        code = ops._kind_code(nms_kind, beta1)
+        # the IoU kind ignores beta1: one graph whatever value came with it
+        rule = (code, float(beta1) if code else 1.0, max(int(top_k), 0))
     key = (tuple(x.shape), str(x.device), float(variances[0]), float(variances[1]),
            float(conf_thres), float(nms_thres), priors.data_ptr()) + rule
     cache = net.__dict__.setdefault("_jabd_graphs", collections.OrderedDict())
@@ -85,8 +95,14 @@ def graphed_detect(net, x, priors, variances, conf_thres=0.5, nms_thres=0.3,
         cache.pop(key, None)
         while len(cache) >= max(1, GRAPH_CACHE):
             cache.popitem(last=False)
-        g = cache[key] = GraphedDetect(net, tuple(x.shape), priors, variances, conf_thres,
-                                       nms_thres, x.device, nms_kind, beta1, top_k)
+        if soft:
+            g = GraphedDetect(net, tuple(x.shape), priors, variances, conf_thres, nms_thres,
+                              x.device, nms_kind, beta1, top_k, sigma=sigma,
+                              soft_offset=soft_offset)
+        else:   # exactly the arguments of the hard kinds
+            g = GraphedDetect(net, tuple(x.shape), priors, variances, conf_thres, nms_thres,
+                              x.device, nms_kind, beta1, top_k)
+        cache[key] = g
     cache.move_to_end(key)
     return g(x)
 
@@ -110,14 +126,20 @@ def _use_graph(net, shape, fixed_shape):
 
 
 def detect_image(net, image, input_shape, cfg, confidence=0.5, nms_iou=0.3,
-                 letterbox_image=True, device="cuda", nms_kind="greedynms", beta1=1.0, top_k=0):
+                 letterbox_image=True, device="cuda", nms_kind="greedynms", beta1=1.0, top_k=0,
+                 sigma=0.5, soft_offset=0.0):
     """image: RGB HWC array (uint8 or float32), as predict.py's np.array(image,
     np.float32).  input_shape = (H, W) of the network input (used only when
     letterbox_image; otherwise the image's own size, as the reference).
     Returns numpy float32 [K, 15] (x1, y1, x2, y2, score, 5 landmark xy) in image
     pixels, NMS order; [] when nothing survives (the reference returns early).
     nms_kind "greedynms" (IoU) or "diounms" with its beta1; top_k > 0 keeps
-    only the top_k best-scored candidates before suppression (ops.detect)."""
+    only the top_k best-scored candidates before suppression (ops.detect).
+    nms_kind "softnms" (alias "softernms"): Gaussian Soft-NMS with `sigma` and
+    `soft_offset`; nms_iou and beta1 are ignored and the rows carry their
+    decayed scores, in the Soft-NMS's result order.  soft_offset defaults to
+    0, not softer_nms's pixel +1: suppression runs on the normalised decode
+    output, where +1 would make every pair overlap."""
     from utils.anchors import Anchors
     img = torch.from_numpy(np.ascontiguousarray(np.asarray(image, np.float32))).to(device)
     ih, iw = int(img.shape[0]), int(img.shape[1])
@@ -128,12 +150,13 @@ def detect_image(net, image, input_shape, cfg, confidence=0.5, nms_iou=0.3,
         if _use_graph(net, (H, W, str(device)), letterbox_image):
             priors = _cached_priors(net, cfg, H, W, device, priors)
             rows, n_keep = graphed_detect(net, x, priors, cfg["variance"], confidence, nms_iou,
-                                          nms_kind, beta1, top_k)
+                                          nms_kind, beta1, top_k, sigma, soft_offset)
         else:
             with F.split_k():
                 loc, conf, landm = net(x)
             rows, n_keep = ops.detect(loc, conf, landm, priors, cfg["variance"], confidence,
-                                      nms_iou, nms_kind=nms_kind, beta1=beta1, top_k=top_k)
+                                      nms_iou, nms_kind=nms_kind, beta1=beta1, top_k=top_k,
+                                      sigma=sigma, soft_offset=soft_offset)
         k = int(n_keep[0].item())
         if k == 0:
             return []

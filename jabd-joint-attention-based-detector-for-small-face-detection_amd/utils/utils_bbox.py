@@ -1,5 +1,5 @@
 """Box decoding and NMS — drop-in for the reference utils/utils_bbox.py
-(decode :29-34, decode_landm :39-46, diounms :182-258, non_max_suppression
+(decode :29-34, decode_landm :39-46, softer_nms :65-114, diounms :182-258, non_max_suppression
 :260-296, retinaface_correct_boxes :9-24) with the device work on the HIP path.
 
 `nms` replaces `torchvision.ops.nms` (same signature and result); the
@@ -64,13 +64,55 @@ def diounms(boxes, scores, overlap=0.5, top_k=200, beta1=1.0):
     return keep, count
 
 
+def softer_nms(dets, confidence=None, thresh=0.01, sigma=0.5, ax=None, offset=1.0):
+    """Gaussian Soft-NMS on the device (reference :65-114): dets [N, C>=5] rows
+    (x1, y1, x2, y2, score, ...).  Each selected row decays the score of every
+    later row it overlaps by exp(-IoU^2 / sigma) (IoU with the reference's
+    "+offset" of pixel boxes); a decayed score below 0.001 drops its row.
+    Returns (rows, keep): rows is a [K, C] device tensor in the reference's
+    result order with the decayed score in column 4, keep the int64 original
+    row indices of those rows.
+
+    Where this departs from the reference (which cannot run as written):
+    * dets is not modified (the reference swaps and rescales it in place);
+    * confidence is not permuted: use confidence[keep];
+    * keep is the original row index of every result row, not range(K).
+    thresh and ax are accepted and ignored, as the reference ignores them."""
+    if dets.dim() != 2 or dets.shape[1] < 5:
+        raise ValueError(f"softer_nms: dets must be [N, >=5], got {tuple(dets.shape)}")
+    det = dets.contiguous()
+    keep, keep_scores, n_keep = ops.batched_soft_nms(
+        det.unsqueeze(0), det[:, 4].contiguous().unsqueeze(0), sigma=sigma, offset=offset)
+    k = int(n_keep[0].item())
+    keep = keep[0, :k]
+    rows = det[keep]
+    rows[:, 4] = keep_scores[0, :k]
+    return rows, keep
+
+
 def non_max_suppression(detection, conf_thres=0.5, nms_thres=0.3, nms_kind="greedynms",
-                        beta1=1.0, top_k=0):
-    """Score filter + NMS (greedy IoU, or "diounms") on the device; returns
-    numpy [K,15] or []."""
+                        beta1=1.0, top_k=0, sigma=0.5, soft_offset=0.0):
+    """Score filter + NMS (greedy IoU, "diounms", or "softnms") on the device;
+    returns numpy [K,15] or [].
+
+    nms_kind "softnms" (alias "softernms"): Gaussian Soft-NMS with `sigma` and
+    `soft_offset`; nms_thres and beta1 are ignored, the rows come in the
+    Soft-NMS's result order and carry their decayed scores.  soft_offset
+    defaults to 0, not softer_nms's pixel +1: the rows here hold normalised
+    decode() output, where +1 would make every pair overlap."""
     if detection.dim() != 2 or detection.shape[1] < 5:
         raise ValueError("non_max_suppression expects [N, >=5] rows")
     det = detection.contiguous()
+    if ops.is_soft_kind(nms_kind):
+        keep, keep_scores, n_keep = ops.batched_soft_nms(
+            det.unsqueeze(0), det[:, 4].contiguous().unsqueeze(0), sigma=sigma,
+            offset=soft_offset, score_threshold=conf_thres, top_k=top_k)
+        k = int(n_keep[0].item())
+        if k == 0:
+            return []
+        rows = det[keep[0, :k]]
+        rows[:, 4] = keep_scores[0, :k]
+        return rows.cpu().numpy()
     keep, n_keep = ops.batched_nms(det.unsqueeze(0), det[:, 4].contiguous().unsqueeze(0),
                                    nms_thres, score_threshold=conf_thres, kind=nms_kind,
                                    beta1=beta1, top_k=top_k)
