@@ -755,7 +755,10 @@ int jabd_nlm_apply_f32(const float* src, int64_t src_bs, int32_t src_ps, int32_t
  * Class (2x2) and Landmark (2x10) 1x1 convs of one pyramid level, written
  * straight into loc [B,A,4] / conf [B,A,2] / landm [B,A,10] at anchor offset
  * a_off (the permute+view+cat layout); softmax over conf pairs if asked.
- * wt [32][C] rows = 8 bbox, 4 class, 20 landmark out channels; bias [32]. */
+ * wt [32][C] rows = 8 bbox, 4 class, 20 landmark out channels; bias [32].
+ * A and a_off must be even (a position's rows are stored as float4),
+ * a_off + 2 HW <= A and B <= 65535; the same holds for jabd_heads_scatter_f32,
+ * jabd_ssh_tail_heads_f32 and jabd_heads_gather_f32. */
 /* 3x3/stride-2/pad-1 max pool, NHWC (torchvision resnet50 stem maxpool). */
 int jabd_maxpool_nhwc_f32(const float* x, int32_t B, int32_t H, int32_t W, int32_t C,
                           int32_t k, int32_t stride, int32_t pad, float* y,

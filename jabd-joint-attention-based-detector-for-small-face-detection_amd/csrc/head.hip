@@ -782,8 +782,10 @@ extern "C" int jabd_heads_f32(const float* x, int64_t x_bs, int32_t x_ps, int32_
                               int64_t a_off, int32_t softmax, float* loc, float* conf,
                               float* landm, jabd_stream_t stream) {
   JABD_REQUIRE(x && wt && bias && loc && conf && landm, "heads: null pointer");
+  JABD_REQUIRE(B > 0 && B <= 65535 && HW > 0 && C > 0, "heads: bad args");
   JABD_REQUIRE(C % 4 == 0 && x_ps % 4 == 0, "heads: C and pixel stride must be multiples of 4");
-  JABD_REQUIRE(a_off + 2 * (int64_t)HW <= A, "heads: anchor range out of bounds");
+  JABD_REQUIRE(A % 2 == 0 && a_off % 2 == 0 && a_off + 2 * (int64_t)HW <= A,
+               "heads: anchor range");
   dim3 g((unsigned)cdiv(HW, 256), (unsigned)B);
   heads_kernel<<<g, 256, 0, as_stream(stream)>>>(
       x, x_bs, x_ps, HW, C, wt, bias, A, a_off, softmax, loc, conf, landm);

@@ -2871,6 +2871,9 @@ extern "C" int jabd_heads_gather_f32(const float* gloc, const float* gconf, cons
                                      int32_t B, int64_t A, int64_t a_off, int32_t HW, float* dout,
                                      jabd_stream_t stream) {
   JABD_REQUIRE(gloc && gconf && glandm && dout, "heads_gather: null");
+  JABD_REQUIRE(B > 0 && B <= 65535 && HW > 0, "heads_gather: bad args");
+  JABD_REQUIRE(A % 2 == 0 && a_off % 2 == 0 && a_off + 2 * (int64_t)HW <= A,
+               "heads_gather: anchor range");
   dim3 g((unsigned)cdiv(HW, 256), (unsigned)B);
   heads_gather_kernel<<<g, 256, 0, as_stream(stream)>>>(gloc, gconf, glandm, A, a_off, HW, dout);
   return check_launch("heads_gather");
