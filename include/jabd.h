@@ -250,7 +250,11 @@ int jabd_detect_soft_f32(const float* loc, const float* conf, const float* landm
  *   priors   [A, 4] (cx,cy,w,h).
  *   loc_t [B,A,4], conf_t int64 [B,A], landm_t [B,A,10] (outputs).
  * Images with zero targets are the caller's error (the reference's `match`
- * fails on them too: max over an empty dim).
+ * fails on them too: max over an empty dim): a batch whose images are all
+ * empty (max_gt == 0) is rejected.  An empty image beside non-empty ones
+ * (offsets[b] == offsets[b+1], which the host cannot see) reads no target
+ * row: its conf_t is 0 for every prior and its loc_t and landm_t are zeros,
+ * from jabd_match_encode_f32 and jabd_match_iou_f32 alike.
  * ------------------------------------------------------------------------ */
 int jabd_match_workspace_size(int64_t batch, int64_t num_priors, size_t* bytes);
 int jabd_match_encode_f32(const float* targets, const int64_t* offsets,

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void match_best_prior_kernel(
   const int b = blockIdx.y;
   const int64_t j = blockIdx.x;
   const int64_t t0 = offsets[b], t1 = offsets[b + 1];
-  if (j >= t1 - t0) return;
+  if (j >= t1 - t0) return;  // every block of an image without targets, too
   const float* tr = targets + (t0 + j) * 15;
   const float tx1 = tr[0], ty1 = tr[1], tx2 = tr[2], ty2 = tr[3];
   const float tarea = (tx2 - tx1) * (ty2 - ty1);
@@ -175,7 +175,9 @@ __global__ __launch_bounds__(256) void match_best_prior_kernel(
 // best_truth per prior (:121-123), forced override (:127-130), threshold
 // (:145), encode (:62-73) and encode_landm (:75-86).  kRaw is match_iou()
 // (nets/retinaface_training_DIOU.py:176-246): the same assignment, but loc_t
-// holds the matched truth box corners (:230-231 `loc = matches`).
+// holds the matched truth box corners (:230-231 `loc = matches`).  An image
+// without targets (the reference fails on it) reads no target row: conf_t 0,
+// loc_t and landm_t zeros (include/jabd.h).
 template <bool kRaw>
 __global__ __launch_bounds__(256) void match_assign_kernel(
     const float* __restrict__ targets, const int64_t* __restrict__ offsets,
@@ -195,6 +197,15 @@ __global__ __launch_bounds__(256) void match_assign_kernel(
   __syncthreads();
   const int64_t a = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (a >= A) return;
+  const int64_t ba = (int64_t)b * A + a;
+  if (ngt <= 0) {  // an image without targets: all background, zero targets
+    conf_t[ba] = 0;
+    reinterpret_cast<float4*>(loc_t)[ba] = make_float4(0.f, 0.f, 0.f, 0.f);
+    float* lm = landm_t + ba * 10;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) lm[k] = 0.f;
+    return;
+  }
   const float4 p = pri[a];
   float px1, py1, px2, py2, pa;
   prior_point_form(p, px1, py1, px2, py2, pa);
@@ -205,7 +216,6 @@ __global__ __launch_bounds__(256) void match_assign_kernel(
                         px1, py1, px2, py2, pa);
     if (better(v, j, bv, bi)) { bv = v; bi = j; }
   }
-  const int64_t ba = (int64_t)b * A + a;
   const int f = forced[ba];
   if (f >= 0) { bv = 2.f; bi = f; }
   const float* tr = targets + (t0 + bi) * 15;

@@ -29,11 +29,8 @@ import numpy as np
 import pytest
 import torch
 
-from _util import rel_err
+from _match_loss_ref import CFG_MNET, _check_loss, _preds
 from oracle import box_ref
-
-CFG_MNET = {"min_sizes": [[16, 32], [64, 128], [256, 512]], "steps": [8, 16, 32],
-            "variance": [0.1, 0.2], "clip": False}
 
 
 def _targets(B, size, seed):
@@ -74,76 +71,6 @@ def _check_match(cuda, tg, pri):
     torch.testing.assert_close(gl.cpu(), rl, rtol=1e-5, atol=1e-5)
     assert torch.equal(glm.cpu(), rlm)
     return rl, rc, rlm
-
-
-def _ulp_band(v, k=4):
-    return k * np.spacing(np.float32(abs(v)) if v != 0 else np.float32(1e-38))
-
-
-def _check_loss(cuda, pri, tg, loc, conf, landm, lt, ct, lmt, exact_sel=False):
-    """Values, OHEM selection and gradients of the device loss vs the oracle.
-    Returns (rows differing near the threshold, exact ties at the threshold)."""
-    from jabd_amd import ops
-    from nets.retinaface_training import MultiBoxLoss
-    leaves = [t.clone().requires_grad_(True) for t in (loc, conf, landm)]
-    rl, rc, rlm, info = box_ref.multibox_loss(*leaves, lt, ct, lmt)
-    (2.0 * rl + rc + rlm).backward()
-
-    # the selection the device loss made (bit 4 of sel), from the same call
-    # the autograd node runs (ops.multibox_sums)
-    d_loc, d_conf, d_landm = (t.to(cuda) for t in (loc, conf, landm))
-    d_lt, d_ct, d_lmt = ops.match_encode([t.to(cuda) for t in tg], pri.to(cuda), 0.35,
-                                         [0.1, 0.2])
-    _, counts, sel = ops.multibox_sums(d_loc, d_conf, d_landm, d_lt, d_ct, d_lmt, 7)
-    got_sel = (sel.cpu() & 4) != 0
-    ref_sel = info["sel"]
-    assert tuple(int(c) for c in counts.cpu()) == info["counts"]
-    mine = info["mining"].detach()
-    near, ties = 0, 0
-    for b in range(loc.shape[0]):
-        npos = int(info["pos"][b].sum())
-        num_neg = min(7 * npos, loc.shape[1] - 1)
-        if num_neg == 0:
-            assert torch.equal(got_sel[b], ref_sel[b])
-            continue
-        thr = float(torch.sort(mine[b], descending=True, stable=True)[0][num_neg - 1])
-        ties += int((mine[b] == thr).sum()) - 1
-        diff = (got_sel[b] ^ ref_sel[b]).nonzero().flatten()
-        if len(diff):
-            band = _ulp_band(thr)
-            assert bool(((mine[b][diff] - thr).abs() <= band).all()), (b, diff[:8])
-            assert int(got_sel[b].sum()) == int(ref_sel[b].sum()), b
-            near += len(diff)
-    print(f"OHEM: {near} rows differ within 4 ulp of a threshold, {ties} exact ties at it")
-    if exact_sel:
-        assert near == 0
-    assert near <= 2 * loc.shape[0], near
-
-    crit = MultiBoxLoss(2, 0.35, 7, [0.1, 0.2], True)
-    gl = [t.to(cuda).requires_grad_(True) for t in (loc, conf, landm)]
-    l, c, lm = crit(tuple(gl), pri.to(cuda), [t.to(cuda) for t in tg])
-    (2.0 * l + c + lm).backward()
-    for got, ref in ((l, rl), (c, rc), (lm, rlm)):
-        got, ref = float(got.detach()), float(ref.detach())
-        assert abs(got - ref) <= 1e-5 * max(1.0, abs(ref)), (got, ref)
-    for g_, r_ in zip(gl, leaves):
-        assert rel_err(g_.grad, r_.grad) < 1e-5
-    return near, ties
-
-
-def _preds(B, A, seed, quant=None):
-    g = torch.Generator().manual_seed(seed)
-    loc = torch.randn(B, A, 4, generator=g)
-    conf = torch.randn(B, A, 2, generator=g) * 2
-    landm = torch.randn(B, A, 10, generator=g)
-    if quant:
-        # background logit 0 and the face logit on a 1/quant grid: equal
-        # mining losses then come from equal (c0, c1) pairs only, so they are
-        # equal in any exp/log implementation (pairs with the same c1 - c0 but
-        # different c0 are equal in exact arithmetic, not in fp32)
-        conf[..., 0] = 0.0
-        conf[..., 1] = torch.round(conf[..., 1] * quant) / quant
-    return loc, conf, landm
 
 
 @pytest.mark.gpu
