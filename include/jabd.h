@@ -242,6 +242,81 @@ int jabd_detect_soft_f32(const float* loc, const float* conf, const float* landm
                          jabd_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * Box voting — the merge step of multi-scale / flip test-time detection,
+ * batched: B independent images of up to n rows (x1, y1, x2, y2, score,
+ * extra...), `cols` >= 5 columns, one workgroup per image.  Each cluster of
+ * overlapping boxes becomes one row holding their score-weighted mean box.
+ * Per image:
+ *   candidates: rows r < n_valid[b] with score >= score_threshold (a NaN score
+ *          fails the comparison and is dropped; -INFINITY keeps every other row)
+ *   order = candidates by descending score, stable: the lower row first among
+ *          equal scores (the total order of jabd_sn_key, csrc/softnms_math.h)
+ *   alive = all candidates
+ *   for seed in order, if alive[seed]:
+ *     o_j     = IoU(seed, j) for every alive j, in fp32 with every operation
+ *               rounded on its own (the "+offset" form of the Soft-NMS above:
+ *               jabd_sn_iou; offset 1 for pixel boxes, 0 for normalised ones)
+ *     members = { j alive : o_j >= (float)vote_threshold } + { seed }
+ *               (a NaN overlap — a NaN coordinate, 0/0 — is no member)
+ *     alive  -= members;  votes = |members|
+ *     if votes >= min_votes:
+ *       box_k = (float)(sum_j (double)score_j * (double)coord_jk
+ *                       / sum_j (double)score_j),   k = 0..3
+ *       emit (box, the seed's score, the seed row's columns 5.. bit for bit)
+ *   result: the emitted rows in seed order, the first max_out of them
+ *          (max_out <= 0: no cap).
+ * The products are exact; the sums are accumulated in double in a fixed order
+ * of the kernel's own (per thread by ascending row, a wave butterfly, the waves
+ * in order) without atomics, so two runs agree bit for bit and a box is within
+ * one fp32 ulp of any other double-precision summation order as long as
+ * nothing cancels.  Seeds, membership, votes and the result order are exact.
+ *   rows   device float, row r of image b at rows + b*row_bstride +
+ *          r*row_stride (strides in floats, row_stride >= cols); not modified.
+ *   out    device float[B, n, cols]: out[b, :n_out[b]] are the result rows.
+ *   n_out  device int64[B].
+ *   seed   device int64[B, n]: the input row index of each result row's seed.
+ *   votes  device int32[B, n]: the member count of each result row.
+ *   owner  device int32[B, n] or NULL: for every input row the result row it
+ *          joined; -1 for a non-candidate and for a member of a cluster
+ *          dropped by min_votes or cut by max_out.
+ * vote_threshold NaN, offset not finite, cols < 5, min_votes < 1 or n >= 2^24
+ * return JABD_EINVAL before any device work.  batch == 0 launches nothing;
+ * n == 0 sets n_out to 0.  No host synchronisation and no memset: the call can
+ * be captured in a HIP graph.  Cost: O(clusters x n_valid) per image on one
+ * workgroup (one sweep over the alive rows and one barrier per cluster).  The
+ * state (box, score, owner: 24 bytes per row) lives in LDS up to n = 6656 and
+ * in the workspace above; the launch witness names the form ("box_vote_lds"
+ * tag 1, "box_vote_ws" tag 2).  The LDS form needs no workspace.
+ * ------------------------------------------------------------------------ */
+int jabd_box_vote_workspace_size(int64_t batch, int64_t n, size_t* bytes);
+int jabd_box_vote_f32(const float* rows, int64_t row_stride, int64_t row_bstride,
+                      int32_t cols, const int64_t* n_valid, int64_t batch, int64_t n,
+                      double vote_threshold, float offset, float score_threshold,
+                      int32_t min_votes, int64_t max_out, float* out, int64_t* n_out,
+                      int64_t* seed, int32_t* votes, int32_t* owner, void* ws,
+                      size_t ws_bytes, jabd_stream_t stream);
+
+/* One pass of a multi-scale / flip test-time detection joins the merged rows
+ * without leaving the device.  rows [n_max, 15] are a pass's jabd_detect rows
+ * (normalised coordinates on the letterboxed canvas), n_keep device int64[1]
+ * their number (clamped to n_max).  For the first n_keep[0] rows, in order:
+ *   1. flip != 0 (the pass ran on the mirrored canvas): x1' = 1 - x2,
+ *      x2' = 1 - x1, every landmark x' = 1 - x — each one fp32 subtraction —
+ *      and the landmark pairs 0 <-> 1 (eyes) and 3 <-> 4 (mouth corners)
+ *      change places;
+ *   2. the arithmetic of jabd_correct_boxes_f32(..., letterbox, to_pixels = 1);
+ *   3. row i is written to merged[offsets[pass] + i]  (merged [cap, 15]).
+ * offsets is a device int64 array of at least pass + 2 entries; the call
+ * reads offsets[pass] (offsets[0] is the caller's) and writes offsets[pass+1]
+ * = min(offsets[pass] + n_keep[0], cap).  Rows that would land at or beyond
+ * cap are dropped: that is the contract, not an error.  No host
+ * synchronisation; one launch. */
+int jabd_tta_collect_f32(const float* rows, const int64_t* n_keep, int64_t n_max,
+                         float* merged, int64_t cap, int64_t* offsets, int32_t pass,
+                         int input_h, int input_w, int image_h, int image_w,
+                         int letterbox, int flip, jabd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * A7/A8 anchor matching + encoding — nets/retinaface_training.py:93-162
  * (match/encode/encode_landm) for a whole batch in one pass.
  *   targets  [T, 15] device fp32: the B per-image target tensors concatenated

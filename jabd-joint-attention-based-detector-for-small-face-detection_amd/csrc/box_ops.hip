@@ -865,17 +865,76 @@ __global__ __launch_bounds__(256) void letterbox_kernel(
 // rescale to image pixels (:195-196) on detection rows [n, 15]: numpy does
 // both in float64 and assigns back into the float32 rows, so each step is
 // (float)((double)v - off) * sc) and (float)((double)v * dim).
-__global__ void correct_rows_kernel(float* __restrict__ rows, int64_t n, int letterbox,
-                                    double offx, double offy, double scx, double scy,
-                                    double dimx, double dimy) {
+struct CorrectArgs {
+  int letterbox;
+  double offx, offy, scx, scy, dimx, dimy;
+};
+
+// column c (not the score column 4) of a row
+__device__ __forceinline__ float correct_value(float v, int c, const CorrectArgs& a) {
+  const bool isx = ((c < 4 ? c : c - 5) & 1) == 0;
+  if (a.letterbox) v = (float)(((double)v - (isx ? a.offx : a.offy)) * (isx ? a.scx : a.scy));
+  return (float)((double)v * (isx ? a.dimx : a.dimy));  // x * 1.0 is exact when !to_pixels
+}
+
+__global__ void correct_rows_kernel(float* __restrict__ rows, int64_t n, CorrectArgs a) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n * 15) return;
   const int c = (int)(i % 15);
   if (c == 4) return;  // the score column is untouched
-  const bool isx = ((c < 4 ? c : c - 5) & 1) == 0;
-  float v = rows[i];
-  if (letterbox) v = (float)(((double)v - (isx ? offx : offy)) * (isx ? scx : scy));
-  rows[i] = (float)((double)v * (isx ? dimx : dimy));  // x * 1.0 is exact when !to_pixels
+  rows[i] = correct_value(rows[i], c, a);
+}
+
+// One pass of a multi-scale / flip test-time detection joins the merged rows:
+// the pass's first n_keep[0] detect rows (normalised canvas coordinates), if
+// `flip` un-mirrored (x -> 1 - x, one fp32 subtraction; the box's x1 and x2
+// change places, and so do the landmark pairs 0 <-> 1, the eyes, and 3 <-> 4,
+// the mouth corners), corrected as correct_rows_kernel does, land at
+// merged[offsets[pass] + i]; rows at or beyond cap are dropped.  One thread per
+// (row, column); thread 0 writes offsets[pass + 1], a slot no thread reads.
+__global__ void tta_collect_kernel(const float* __restrict__ rows,
+                                   const int64_t* __restrict__ n_keep, int64_t n_max,
+                                   float* __restrict__ merged, int64_t cap,
+                                   int64_t* __restrict__ offsets, int pass, int flip,
+                                   CorrectArgs a) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t nk = n_keep[0];
+  nk = nk < 0 ? 0 : (nk > n_max ? n_max : nk);
+  int64_t base = offsets[pass];
+  base = base < 0 ? 0 : (base > cap ? cap : base);
+  if (i == 0) offsets[pass + 1] = base + nk < cap ? base + nk : cap;
+  const int64_t r = i / 15;
+  const int c = (int)(i - r * 15);
+  if (r >= nk || base + r >= cap) return;
+  const float* src = rows + r * 15;
+  float v;
+  if (!flip || c == 4) {
+    v = src[c];
+  } else if (c < 4) {
+    v = (c & 1) ? src[c] : 1.f - src[2 - c];
+  } else {
+    const int k = (c - 5) >> 1;  // landmark k takes its mirror partner's place
+    const int ks = k == 0 ? 1 : (k == 1 ? 0 : (k == 3 ? 4 : (k == 4 ? 3 : 2)));
+    const float s = src[5 + 2 * ks + ((c - 5) & 1)];
+    v = ((c - 5) & 1) ? s : 1.f - s;
+  }
+  merged[(base + r) * 15 + c] = c == 4 ? v : correct_value(v, c, a);
+}
+
+// utils_bbox.py:10-12, numpy float64 over [h, w] pairs
+static CorrectArgs correct_args(int input_h, int input_w, int image_h, int image_w,
+                                int letterbox, int to_pixels) {
+  CorrectArgs a{letterbox, 0, 0, 1, 1, to_pixels ? (double)image_w : 1.0,
+                to_pixels ? (double)image_h : 1.0};
+  if (letterbox) {
+    const double r = fmin((double)input_h / image_h, (double)input_w / image_w);
+    const double nh = image_h * r, nw = image_w * r;
+    a.offy = (input_h - nh) / 2. / input_h;
+    a.offx = (input_w - nw) / 2. / input_w;
+    a.scy = input_h / nh;
+    a.scx = input_w / nw;
+  }
+  return a;
 }
 
 }  // namespace jabd
@@ -889,20 +948,27 @@ extern "C" int jabd_correct_boxes_f32(float* rows, int64_t n, int input_h, int i
   JABD_REQUIRE(!letterbox || (input_h > 0 && input_w > 0), "correct_boxes: bad input shape");
   if (n == 0) return JABD_OK;
   JABD_REQUIRE(rows, "correct_boxes: null pointer");
-  // utils_bbox.py:10-12, numpy float64 over [h, w] pairs
-  double offx = 0, offy = 0, scx = 1, scy = 1;
-  if (letterbox) {
-    const double r = fmin((double)input_h / image_h, (double)input_w / image_w);
-    const double nh = image_h * r, nw = image_w * r;
-    offy = (input_h - nh) / 2. / input_h;
-    offx = (input_w - nw) / 2. / input_w;
-    scy = input_h / nh;
-    scx = input_w / nw;
-  }
   correct_rows_kernel<<<(unsigned)cdiv(n * 15, 256), 256, 0, as_stream(stream)>>>(
-      rows, n, letterbox, offx, offy, scx, scy, to_pixels ? (double)image_w : 1.0,
-      to_pixels ? (double)image_h : 1.0);
+      rows, n, correct_args(input_h, input_w, image_h, image_w, letterbox, to_pixels));
   return check_launch("correct_boxes");
+}
+
+extern "C" int jabd_tta_collect_f32(const float* rows, const int64_t* n_keep, int64_t n_max,
+                                    float* merged, int64_t cap, int64_t* offsets, int32_t pass,
+                                    int input_h, int input_w, int image_h, int image_w,
+                                    int letterbox, int flip, jabd_stream_t stream) {
+  JABD_REQUIRE(n_max >= 0 && cap >= 0 && pass >= 0, "tta_collect: bad size");
+  JABD_REQUIRE(image_h > 0 && image_w > 0, "tta_collect: bad image shape");
+  JABD_REQUIRE(!letterbox || (input_h > 0 && input_w > 0), "tta_collect: bad input shape");
+  JABD_REQUIRE(n_max < (int64_t(1) << 31), "tta_collect: n_max=%lld too large",
+               (long long)n_max);
+  JABD_REQUIRE(n_keep && offsets, "tta_collect: null pointer");
+  JABD_REQUIRE((rows || n_max == 0) && (merged || cap == 0), "tta_collect: null pointer");
+  const int64_t blocks = cdiv(n_max * 15, 256);
+  tta_collect_kernel<<<(unsigned)(blocks < 1 ? 1 : blocks), 256, 0, as_stream(stream)>>>(
+      rows, n_keep, n_max, merged, cap, offsets, (int)pass, flip ? 1 : 0,
+      correct_args(input_h, input_w, image_h, image_w, letterbox, 1));
+  return check_launch("tta_collect");
 }
 
 extern "C" int jabd_letterbox_f32(const float* src, int64_t batch, int ih, int iw, float* dst,

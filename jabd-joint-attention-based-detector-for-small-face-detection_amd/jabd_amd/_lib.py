@@ -134,6 +134,12 @@ SIGNATURES = {
     "jabd_detect_soft_workspace_size": [c_i64, c_i64, c_sizep],
     "jabd_detect_soft_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32,
                              c_f64, c_f32, c_f64, c_i64, c_vp, c_vp, c_vp, c_size, c_vp],
+    "jabd_box_vote_workspace_size": [c_i64, c_i64, c_sizep],
+    "jabd_box_vote_f32": [c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_i64,
+                          c_f64, c_f32, c_f32, c_i32, c_i64,   # vote thr, offset, score thr,
+                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp],  # min_votes, max_out
+    "jabd_tta_collect_f32": [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_int, c_int, c_int,
+                             c_int, c_int, c_int, c_vp],
     "jabd_match_workspace_size": [c_i64, c_i64, c_sizep],
     "jabd_match_encode_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_f32, c_f32, c_f32,
                               c_vp, c_vp, c_vp, c_vp, c_size, c_vp],

@@ -227,6 +227,94 @@ def batched_soft_nms(boxes, scores, sigma=0.5, offset=1.0, score_threshold=-math
     return keep, keep_scores, n_keep
 
 
+# --------------------------------------------------------------------------- box voting
+def _vote_args(vote_threshold, offset, min_votes, cols=5):
+    vote_threshold, offset, min_votes = float(vote_threshold), float(offset), int(min_votes)
+    if math.isnan(vote_threshold):
+        raise ValueError("box_vote: vote_threshold is NaN")
+    if not math.isfinite(offset):
+        raise ValueError(f"box_vote: offset must be finite, got {offset!r}")
+    if min_votes < 1:
+        raise ValueError(f"box_vote: min_votes must be at least 1, got {min_votes!r}")
+    if cols < 5:
+        raise ValueError(f"box_vote: rows need at least 5 columns, got {cols}")
+    return vote_threshold, offset, min_votes
+
+
+def box_vote(rows, vote_threshold=0.4, offset=1.0, score_threshold=-math.inf, min_votes=1,
+             max_out=750, n_valid=None, return_owner=False):
+    """Box voting per image (semantics: jabd_box_vote_f32 in jabd.h): each
+    cluster of boxes whose IoU with the cluster's best-scored box (the seed) is
+    >= vote_threshold becomes one row with the score-weighted mean box, the
+    seed's score and the seed's other columns.
+
+    rows [B, N, C>=5] device float32 (x1, y1, x2, y2, score, ...), not
+    modified.  Returns (out [B,N,C], n_out [B] int64, seed [B,N] int64, votes
+    [B,N] int32[, owner [B,N] int32]) on the device: out[b,:n_out[b]] are the
+    result rows in seed order (descending score), seed their seeds' input row
+    indices, votes their member counts, owner the result row each input row
+    joined (-1: none).  Clusters of fewer than min_votes members are dropped;
+    at most max_out rows are returned (max_out <= 0: no cap).  offset: 1 for
+    pixel boxes, 0 for normalised ones.  Candidates: rows < n_valid[b] with
+    score >= score_threshold (NaN scores are dropped).
+    """
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 3:
+        raise ValueError("box_vote: rows must be a [B, N, >=5] tensor")
+    vote_threshold, offset, min_votes = _vote_args(vote_threshold, offset, min_votes,
+                                                   rows.shape[-1])
+    B, N, C = rows.shape
+    if N >= 1 << 24:
+        raise ValueError(f"box_vote: N={N} exceeds 2^24 rows per image")
+    rows = _dev("box_vote.rows", rows)
+    dev = rows.device
+    out = torch.empty((B, N, C), dtype=torch.float32, device=dev)
+    n_out = torch.empty((B,), dtype=torch.int64, device=dev)   # written by every call
+    seed = torch.empty((B, N), dtype=torch.int64, device=dev)
+    votes = torch.empty((B, N), dtype=torch.int32, device=dev)
+    owner = torch.empty((B, N), dtype=torch.int32, device=dev) if return_owner else None
+    if n_valid is not None:
+        n_valid = _dev("box_vote.n_valid", n_valid, torch.int64)
+        if n_valid.numel() != B:
+            raise ValueError(f"box_vote: n_valid has {n_valid.numel()} entries for {B} images")
+    ws = _ws(_size_query("jabd_box_vote_workspace_size", B, N), dev)
+    call("jabd_box_vote_f32", _p(rows), C, N * C, C, _p(n_valid), B, N, vote_threshold, offset,
+         float(score_threshold), min_votes, int(max_out), _p(out), _p(n_out), _p(seed),
+         _p(votes), _p(owner), _p(ws), ws.numel(), _stream())
+    return (out, n_out, seed, votes, owner) if return_owner else (out, n_out, seed, votes)
+
+
+def tta_collect(rows, n_keep, merged, offsets, pass_index, input_shape, image_shape,
+                letterbox=True, flip=False):
+    """One pass of a multi-scale / flip detection joins `merged` on the device
+    (jabd_tta_collect_f32): the first n_keep[0] of the pass's detect rows
+    [n_max, 15], un-mirrored if `flip` (the pass ran on the mirrored canvas),
+    corrected to image pixels as correct_boxes(..., letterbox, to_pixels=True),
+    are written from merged[offsets[pass_index]] on, and offsets[pass_index+1]
+    = min(offsets[pass_index] + n_keep[0], len(merged)).  Rows beyond the
+    capacity of merged [cap, 15] are dropped.  offsets: device int64 of at
+    least pass_index + 2 entries, offsets[0] set by the caller.  input_shape =
+    (H, W) of the network input, image_shape = (im_height, im_width).  No
+    host synchronisation.  Returns merged."""
+    rows = _dev("tta_collect.rows", rows)
+    n_keep = _dev("tta_collect.n_keep", n_keep, torch.int64)
+    if rows.dim() != 2 or rows.shape[1] != 15:
+        raise ValueError(f"tta_collect: rows must be [n, 15], got {tuple(rows.shape)}")
+    for name, t, dt in (("merged", merged, torch.float32), ("offsets", offsets, torch.int64)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt
+                and t.is_contiguous()):
+            raise ValueError(f"tta_collect: {name} must be a contiguous device {dt} tensor")
+    if merged.dim() != 2 or merged.shape[1] != 15:
+        raise ValueError(f"tta_collect: merged must be [cap, 15], got {tuple(merged.shape)}")
+    p = int(pass_index)
+    if p < 0 or offsets.dim() != 1 or offsets.numel() < p + 2 or n_keep.numel() < 1:
+        raise ValueError("tta_collect: offsets needs pass_index + 2 entries, n_keep one")
+    call("jabd_tta_collect_f32", _p(rows), _p(n_keep), rows.shape[0], _p(merged),
+         merged.shape[0], _p(offsets), p, int(input_shape[0]), int(input_shape[1]),
+         int(image_shape[0]), int(image_shape[1]), 1 if letterbox else 0, 1 if flip else 0,
+         _stream())
+    return merged
+
+
 def detect(loc, conf, landm, priors, variances, conf_threshold=0.5, nms_threshold=0.3,
            nms_kind="greedynms", beta1=1.0, top_k=0, sigma=0.5, soft_offset=0.0):
     """predict.py:162-181 on device for a batch: decode + filter + NMS.

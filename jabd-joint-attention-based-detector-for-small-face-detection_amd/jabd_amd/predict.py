@@ -165,6 +165,96 @@ def detect_image(net, image, input_shape, cfg, confidence=0.5, nms_iou=0.3,
     return det.cpu().numpy()
 
 
+def _tta_passes(net, img, cfg, scales, flip, confidence, nms_iou, device, nms_kind, beta1, top_k):
+    """The passes of detect_image_tta: (rows [A, 15], n_keep [1], (H, W),
+    mirrored) one after the other, each valid until the next is asked for (a
+    graphed pass hands out its graph's static buffers)."""
+    from utils.anchors import Anchors
+    ih, iw = int(img.shape[0]), int(img.shape[1])
+    plan = []
+    for s in scales:
+        H = 32 * max(1, round(ih * float(s) / 32))
+        W = 32 * max(1, round(iw * float(s) / 32))
+        priors = Anchors(cfg, image_size=(H, W)).get_anchors().to(device).float().contiguous()
+        graph = _use_graph(net, (H, W, str(device)), False)
+        if graph:
+            priors = _cached_priors(net, cfg, H, W, device, priors)
+        plan.append((H, W, priors, graph))
+    total = sum(p[2].shape[0] for p in plan) * (2 if flip else 1)
+
+    def run():
+        for H, W, priors, graph in plan:
+            x = ops.letterbox(img, (W, H), mean=(104.0, 117.0, 123.0))   # [1, 3, H, W]
+            for mirrored in ((False, True) if flip else (False,)):
+                # the canvas is mirrored, not the image: 1 - x un-mirrors it exactly
+                xin = x.flip(-1).contiguous() if mirrored else x
+                if graph:
+                    rows, n_keep = graphed_detect(net, xin, priors, cfg["variance"], confidence,
+                                                  nms_iou, nms_kind, beta1, top_k)
+                else:
+                    with F.split_k():
+                        loc, conf, landm = net(xin)
+                    rows, n_keep = ops.detect(loc, conf, landm, priors, cfg["variance"],
+                                              confidence, nms_iou, nms_kind=nms_kind, beta1=beta1,
+                                              top_k=top_k)
+                yield rows[0], n_keep, (H, W), mirrored
+    return total, run()
+
+
+def detect_image_tta(net, image, cfg, scales=(0.5, 1.0, 1.5, 2.0), flip=True, confidence=0.5,
+                     nms_iou=0.3, vote_thres=0.4, min_votes=1, max_out=750, device="cuda",
+                     nms_kind="greedynms", beta1=1.0, top_k=0, _merged_hook=None):
+    """Multi-scale / flip test-time detection with box voting, on the device.
+    image: RGB HWC array as detect_image takes it.  For every scale s the image
+    is letterboxed to a network input of H = 32 max(1, round(ih s / 32)), W
+    likewise, and detected (detect_image's forward + decode + filter + NMS with
+    `confidence`, `nms_iou`, `nms_kind`, `beta1`, `top_k`), plain and, with
+    `flip`, on the mirrored canvas.  Each pass's rows are un-mirrored, brought
+    to image pixels and appended to one merged list on the device
+    (ops.tta_collect); ops.box_vote (IoU >= vote_thres with the pixel +1,
+    min_votes, max_out) then replaces each cluster of overlapping rows by one
+    row: the score-weighted mean box with the best member's score and
+    landmarks.  Returns numpy float32 [K, 15] in image pixels, descending
+    score; [] when nothing survives.  The call synchronises with the device
+    once, reading the number of result rows (max_out <= 0: once more for the
+    rows).  A shape recurs in a HIP graph as in detect_image without
+    letterbox_image: from the second call with the same image size on.
+    _merged_hook(merged, offsets), if given, sees the device buffers the
+    passes were collected into just before the vote (offsets[-1] rows are
+    valid); the tests read the voting step's input through it."""
+    img = torch.from_numpy(np.ascontiguousarray(np.asarray(image, np.float32))).to(device)
+    ih, iw = int(img.shape[0]), int(img.shape[1])
+    scales = tuple(scales)
+    if not scales:
+        raise ValueError("detect_image_tta: no scales")
+    ops._vote_args(vote_thres, 1.0, min_votes)
+    with torch.no_grad():
+        cap, passes = _tta_passes(net, img, cfg, scales, flip, confidence, nms_iou, device,
+                                  nms_kind, beta1, top_k)
+        n_pass = len(scales) * (2 if flip else 1)
+        merged = torch.empty((cap, 15), dtype=torch.float32, device=img.device)
+        offsets = torch.zeros(n_pass + 1, dtype=torch.int64, device=img.device)
+        for p, (rows, n_keep, shape, mirrored) in enumerate(passes):
+            ops.tta_collect(rows, n_keep, merged, offsets, p, shape, (ih, iw), letterbox=True,
+                            flip=mirrored)
+        if _merged_hook is not None:
+            _merged_hook(merged, offsets)
+        out, n_out, _, _ = ops.box_vote(merged.unsqueeze(0), vote_threshold=vote_thres,
+                                        offset=1.0, min_votes=min_votes, max_out=max_out,
+                                        n_valid=offsets[n_pass:])
+        if max_out > 0:
+            # the rows that can be asked for travel with the count: one synchronisation
+            bound = min(int(max_out), cap)
+            host = torch.empty((bound, 15), dtype=torch.float32, pin_memory=True)
+            host.copy_(out[0, :bound], non_blocking=True)
+            k = int(n_out[0].item())
+            return host[:k].numpy().copy() if k else []
+        k = int(n_out[0].item())
+        if k == 0:
+            return []
+        return out[0, :k].cpu().numpy()
+
+
 def _cached_priors(net, cfg, H, W, device, priors):
     """One priors tensor per (input size, device, anchor cfg) on the module
     (the graph keys on its storage).  The priors are a function of exactly

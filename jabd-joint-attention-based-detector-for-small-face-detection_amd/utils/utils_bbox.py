@@ -90,6 +90,27 @@ def softer_nms(dets, confidence=None, thresh=0.01, sigma=0.5, ax=None, offset=1.
     return rows, keep
 
 
+def bbox_vote(det, thresh=0.4, min_votes=1, max_out=750, offset=1.0):
+    """Box voting on the device (ops.box_vote) for one image's rows [N, C>=5]
+    (x1, y1, x2, y2, score, ...), a device tensor or a numpy array: the merge
+    step of multi-scale / flip testing.  Taking the rows in descending score
+    order, each still unmerged row gathers the unmerged rows whose IoU with it
+    ("+offset" form: 1 for pixel boxes) is >= thresh; the cluster becomes one
+    row with the score-weighted mean box, the best row's score and its other
+    columns.  Clusters of fewer than min_votes rows are dropped, at most
+    max_out rows returned.  Returns numpy [K, C], or [] when K is 0."""
+    if not isinstance(det, torch.Tensor):
+        det = torch.from_numpy(np.ascontiguousarray(np.asarray(det, np.float32))).to("cuda")
+    if det.dim() != 2 or det.shape[1] < 5:
+        raise ValueError(f"bbox_vote: det must be [N, >=5], got {tuple(det.shape)}")
+    out, n_out, _, _ = ops.box_vote(det.contiguous().unsqueeze(0), vote_threshold=thresh,
+                                    offset=offset, min_votes=min_votes, max_out=max_out)
+    k = int(n_out[0].item())
+    if k == 0:
+        return []
+    return out[0, :k].cpu().numpy()
+
+
 def non_max_suppression(detection, conf_thres=0.5, nms_thres=0.3, nms_kind="greedynms",
                         beta1=1.0, top_k=0, sigma=0.5, soft_offset=0.0):
     """Score filter + NMS (greedy IoU, "diounms", or "softnms") on the device;
