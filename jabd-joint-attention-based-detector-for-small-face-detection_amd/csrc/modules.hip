@@ -21,7 +21,8 @@ __device__ __forceinline__ float mact(float v, int act, float slope) {
     case ACT_RELU: return relu_f(v);
     case ACT_LEAKY: return v > 0.f ? v : v * slope;
     case ACT_HSWISH: return hswish_f(v);
-    case ACT_HSIGMOID: return hsigmoid_f(v);
+    // nn.Hardsigmoid keeps a NaN; hsigmoid_f's fmed3 returns min3 (0) for one
+    case ACT_HSIGMOID: return v != v ? v : hsigmoid_f(v);
     case ACT_SIGMOID: return 1.f / (1.f + expf(-v));
     default: return v;
   }
@@ -220,8 +221,11 @@ __global__ __launch_bounds__(256) void pool_bins_kernel(const float* __restrict_
 }
 
 // dx[b][p][c] = sum over the bins containing p of dy[b][s][c] / |bin s|
-// (gather form: every pixel owns its sum, no atomics).  Per level only the
-// bins around floor(i*z/H) can hold row i (likewise for columns).
+// (gather form: every pixel owns its sum, no atomics).  Bin bi of a level
+// holds row i iff floor(bi*H/z) <= i < ceil((bi+1)*H/z), i.e. for bi in
+// [floor(i*z/H), ceil((i+1)*z/H) - 1]: one to three bins when z <= H, about
+// z/H + 1 of them when z > H (likewise for columns).  Levels, then bi, then
+// bj ascending: a fixed summation order.
 __global__ __launch_bounds__(256) void adaptive_pool_bwd_kernel(const float* __restrict__ dy,
                                                                 int H, int W, int C,
                                                                 const PoolSizes sz, int S,
@@ -236,8 +240,8 @@ __global__ __launch_bounds__(256) void adaptive_pool_bwd_kernel(const float* __r
   int base = 0;
   for (int l = 0; l < sz.n; ++l) {
     const int z = sz.v[l];
-    const int bi0 = max(0, (i * z) / H - 1), bi1 = min(z - 1, (i * z) / H + 1);
-    const int bj0 = max(0, (j * z) / W - 1), bj1 = min(z - 1, (j * z) / W + 1);
+    const int bi0 = (i * z) / H, bi1 = min(z - 1, ((i + 1) * z - 1) / H);
+    const int bj0 = (j * z) / W, bj1 = min(z - 1, ((j + 1) * z - 1) / W);
     for (int bi = bi0; bi <= bi1; ++bi) {
       const int r0 = (bi * H) / z, r1 = ((bi + 1) * H + z - 1) / z;
       if (i < r0 || i >= r1) continue;
@@ -338,7 +342,9 @@ extern "C" int jabd_bn_eval_f32(const float* x, int64_t M, int32_t C, const floa
                                 const float* running_var, float eps, const float* gamma,
                                 const float* beta, int32_t act, float slope, float* y,
                                 jabd_stream_t stream) {
-  JABD_REQUIRE(x && running_mean && running_var && gamma && beta && y && M >= 0 && C > 0,
+  // (an empty batch has no storage: x and y may be null when M == 0, as in jabd_act_f32)
+  JABD_REQUIRE(running_mean && running_var && gamma && beta && M >= 0 && C > 0 &&
+                   (M == 0 || (x && y)),
                "bn_eval: bad args");
   JABD_REQUIRE(act >= ACT_NONE && act <= ACT_SIGMOID, "bn_eval: act %d", act);
   if (M == 0) return JABD_OK;
