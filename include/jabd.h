@@ -317,6 +317,69 @@ int jabd_tta_collect_f32(const float* rows, const int64_t* n_keep, int64_t n_max
                          int letterbox, int flip, jabd_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * Tiled (sliced) detection of a large image: overlapping fixed-size tiles
+ * run as one batch through the fixed-shape forward, and their detect rows
+ * are merged in image pixels without leaving the device.
+ *
+ * jabd_tile_gather_f32: the image -> tile-batch step.
+ *   src      device HWC image [ih, iw, 3], float32 (src_is_u8 = 0, 16-byte
+ *            aligned) or uint8 (src_is_u8 != 0, 4-byte aligned).
+ *   origins  device int32 [n_tiles, 2] = (y0, x0) of each tile; may be
+ *            negative or reach past the image.
+ *   dst      device float32 [n_tiles, 3, tile_h, tile_w], 16-byte aligned:
+ *            dst[t, c, y, x] = P - mean3[c], P = (float)src[y0+y, x0+x, c]
+ *            when that pixel lies inside [0, ih) x [0, iw), else `fill`.
+ *            The uint8 conversion is exact.
+ *   mean3    host float[3].
+ * n_tiles == 0 launches nothing.  One launch; 16-byte plane stores, and
+ * 16-byte (uint8: 4-byte) loads where four consecutive pixels lie inside the
+ * image and start on such a boundary (launch tag 4; a tile_w that is no
+ * multiple of 4 takes the one-pixel form, tag 1).
+ *
+ * jabd_tile_collect_f32: a batch of tiles' jabd_detect rows joins the merged
+ * list, as jabd_tta_collect_f32 does it for one pass.  rows [n_slots, A, 15]
+ * (normalised tile coordinates), n_keep device int64 [n_slots]; only the
+ * first n_tiles <= n_slots slots are read.  For tile t and row
+ * r < clamp(n_keep[t], 0, A), with (y0, x0) = origins[t] and, in double,
+ * bx1 = x1 * tile_w, bx2 = x2 * tile_w, by1 = y1 * tile_h, by2 = y2 * tile_h:
+ *   edge filter  the row is dropped if
+ *                  x0 > 0 && bx1 < border, or
+ *                  x0 + tile_w < image_w && bx2 > tile_w - border, or
+ *                  y0 > 0 && by1 < border, or
+ *                  y0 + tile_h < image_h && by2 > tile_h - border
+ *                (a tile side on or beyond the image boundary never filters;
+ *                a NaN compares false, so such a row is kept; border =
+ *                -INFINITY switches the filter off);
+ *   survivors    every x column (box and landmarks) becomes
+ *                (float)((double)v * tile_w + x0), every y column
+ *                (float)((double)v * tile_h + y0); the score is copied —
+ *                the bits of jabd_correct_boxes_f32(..., letterbox = 0,
+ *                to_pixels = 1) when the origin is 0;
+ *   placement    survivor k, counted in ascending tile order and within a
+ *                tile in row order, lands at merged[offsets[pass] + k]
+ *                (merged [cap, 15]); rows at or beyond cap are dropped, and
+ *                offsets[pass+1] = min(offsets[pass] + survivors, cap).
+ * The position comes from a scan (a per-tile ballot/prefix launch writing
+ * ranks and counts to the workspace, then a scatter launch), never from the
+ * arrival order of atomics: two runs give identical bytes.  offsets: device
+ * int64 of at least pass + 2 entries, as jabd_tta_collect_f32, so both calls
+ * can extend one chain.  No host synchronisation (n_keep and offsets are read
+ * on the device) and no memset: the call can be captured in a HIP graph.
+ * n_tiles == 0 or A == 0: offsets[pass+1] = offsets[pass].  n_tiles <= 65535,
+ * A * 15 < 2^31; a NaN border returns JABD_EINVAL.
+ * ------------------------------------------------------------------------ */
+int jabd_tile_gather_f32(const void* src, int src_is_u8, int ih, int iw,
+                         const int32_t* origins, int64_t n_tiles, int tile_h,
+                         int tile_w, float fill, const float* mean3, float* dst,
+                         jabd_stream_t stream);
+int jabd_tile_collect_workspace_size(int64_t n_tiles, int64_t A, size_t* bytes);
+int jabd_tile_collect_f32(const float* rows, const int64_t* n_keep, int64_t n_tiles,
+                          int64_t A, const int32_t* origins, int tile_h, int tile_w,
+                          int image_h, int image_w, float border, float* merged,
+                          int64_t cap, int64_t* offsets, int32_t pass, void* ws,
+                          size_t ws_bytes, jabd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * A7/A8 anchor matching + encoding — nets/retinaface_training.py:93-162
  * (match/encode/encode_landm) for a whole batch in one pass.
  *   targets  [T, 15] device fp32: the B per-image target tensors concatenated

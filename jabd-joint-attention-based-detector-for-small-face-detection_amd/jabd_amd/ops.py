@@ -315,6 +315,81 @@ def tta_collect(rows, n_keep, merged, offsets, pass_index, input_shape, image_sh
     return merged
 
 
+# --------------------------------------------------------------------------- tiled detection
+def _tile_origins(name, origins):
+    origins = _dev(name + ".origins", origins, torch.int32)
+    if origins.dim() != 2 or origins.shape[1] != 2:
+        raise ValueError(f"{name}: origins must be int32 [n_tiles, 2], got "
+                         f"{tuple(origins.shape)}")
+    return origins
+
+
+def tile_gather(image, origins, tile, fill=84.0, mean=(104.0, 117.0, 123.0)):
+    """The tile batch of an image (jabd_tile_gather_f32): image device HWC
+    [ih, iw, 3], float32 or uint8; origins device int32 [T, 2] = (y0, x0), which
+    may be negative or reach past the image; tile = (tile_h, tile_w).  Returns
+    float32 [T, 3, tile_h, tile_w] with out[t, c, y, x] = P - mean[c], P the
+    image's pixel (y0 + y, x0 + x) or `fill` outside the image."""
+    if not isinstance(image, torch.Tensor) or image.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("tile_gather: image must be a float32 or uint8 tensor")
+    image = _dev("tile_gather.image", image, image.dtype)
+    if image.dim() != 3 or image.shape[2] != 3 or image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError(f"tile_gather: image must be [ih, iw, 3], got {tuple(image.shape)}")
+    origins = _tile_origins("tile_gather", origins)
+    th, tw = int(tile[0]), int(tile[1])
+    if th < 1 or tw < 1:
+        raise ValueError(f"tile_gather: bad tile {tile!r}")
+    T = origins.shape[0]
+    out = torch.empty((T, 3, th, tw), dtype=torch.float32, device=image.device)
+    m =(ctypes.c_float * 3)(*[float(v) for v in mean])
+    call("jabd_tile_gather_f32", _p(image), 1 if image.dtype == torch.uint8 else 0,
+         image.shape[0], image.shape[1], _p(origins), T, th, tw, float(fill),
+         ctypes.cast(m, ctypes.c_void_p), _p(out), _stream())
+    return out
+
+
+def tile_collect(rows, n_keep, origins, merged, offsets, pass_index, tile, image_shape,
+                 border=1.0):
+    """A batch of tiles' detect rows joins `merged` on the device
+    (jabd_tile_collect_f32).  rows [n_slots, A, 15] and n_keep [n_slots] are
+    ops.detect's outputs for a tile batch, origins device int32 [T, 2] (T <=
+    n_slots: only the first T slots are read), tile = (tile_h, tile_w),
+    image_shape = (im_height, im_width).  A row whose box comes within `border`
+    tile pixels of a tile side that lies inside the image is dropped (the tile
+    cut the face: a neighbouring tile sees it whole); the others are brought to
+    image pixels and written, in tile and row order, from
+    merged[offsets[pass_index]] on; offsets[pass_index + 1] = min(offsets[
+    pass_index] + survivors, len(merged)).  border=-inf keeps every row.
+    offsets as ops.tta_collect takes it: both can extend one chain.  No host
+    synchronisation.  Returns merged."""
+    rows = _dev("tile_collect.rows", rows)
+    n_keep = _dev("tile_collect.n_keep", n_keep, torch.int64)
+    origins = _tile_origins("tile_collect", origins)
+    if rows.dim() != 3 or rows.shape[2] != 15:
+        raise ValueError(f"tile_collect: rows must be [n_slots, A, 15], got {tuple(rows.shape)}")
+    S, A = rows.shape[0], rows.shape[1]
+    T = origins.shape[0]
+    if T > S or n_keep.numel() < T:
+        raise ValueError(f"tile_collect: {T} origins for {S} slots and {n_keep.numel()} counts")
+    for name, t, dt in (("merged", merged, torch.float32), ("offsets", offsets, torch.int64)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt
+                and t.is_contiguous()):
+            raise ValueError(f"tile_collect: {name} must be a contiguous device {dt} tensor")
+    if merged.dim() != 2 or merged.shape[1] != 15:
+        raise ValueError(f"tile_collect: merged must be [cap, 15], got {tuple(merged.shape)}")
+    p = int(pass_index)
+    if p < 0 or offsets.dim() != 1 or offsets.numel() < p + 2:
+        raise ValueError("tile_collect: offsets needs pass_index + 2 entries")
+    border = float(border)
+    if math.isnan(border):
+        raise ValueError("tile_collect: border is NaN")
+    ws = _ws(_size_query("jabd_tile_collect_workspace_size", T, A), rows.device)
+    call("jabd_tile_collect_f32", _p(rows), _p(n_keep), T, A, _p(origins), int(tile[0]),
+         int(tile[1]), int(image_shape[0]), int(image_shape[1]), border, _p(merged),
+         merged.shape[0], _p(offsets), p, _p(ws), ws.numel(), _stream())
+    return merged
+
+
 def detect(loc, conf, landm, priors, variances, conf_threshold=0.5, nms_threshold=0.3,
            nms_kind="greedynms", beta1=1.0, top_k=0, sigma=0.5, soft_offset=0.0):
     """predict.py:162-181 on device for a batch: decode + filter + NMS.

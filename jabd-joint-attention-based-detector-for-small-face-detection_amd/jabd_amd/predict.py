@@ -255,15 +255,176 @@ def detect_image_tta(net, image, cfg, scales=(0.5, 1.0, 1.5, 2.0), flip=True, co
         return out[0, :k].cpu().numpy()
 
 
+def _pair(name, v):
+    """(a, b) from an int or a pair of ints."""
+    try:
+        a, b = (v, v) if isinstance(v, (int, np.integer)) else v
+        if int(a) != a or int(b) != b:
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be an int or a pair of ints, got {v!r}") from None
+    return int(a), int(b)
+
+
+def tile_plan(ih, iw, tile=(1024, 1024), overlap=(128, 128)):
+    """The tile origins of sliced detection: int32 [T, 2] = (y0, x0),
+    row-major (y outer).  Per axis of length L with tile t and overlap o:
+    stride = t - o, n = 1 if L <= t else ceil((L - t) / stride) + 1, origin k =
+    min(k * stride, L - t) (0 when L <= t): the tiles cover the axis, the last
+    is flush with its end, and neighbours share at least o pixels.  tile sides
+    must be positive multiples of 32 (the network's stride) and 0 <= o < t;
+    anything else raises ValueError."""
+    th, tw = _pair("tile", tile)
+    oy, ox = _pair("overlap", overlap)
+    if int(ih) != ih or int(iw) != iw or ih < 1 or iw < 1:
+        raise ValueError(f"tile_plan: bad image size {ih!r} x {iw!r}")
+    axes = []
+    for L, t, o in ((int(ih), th, oy), (int(iw), tw, ox)):
+        if t < 32 or t % 32:
+            raise ValueError(f"tile_plan: tile side {t} is no positive multiple of 32")
+        if not 0 <= o < t:
+            raise ValueError(f"tile_plan: overlap {o} outside [0, {t})")
+        stride = t - o
+        n = 1 if L <= t else -(-(L - t) // stride) + 1
+        axes.append([min(k * stride, max(L - t, 0)) for k in range(n)])
+    return np.array([(y, x) for y in axes[0] for x in axes[1]], np.int32).reshape(-1, 2)
+
+
+# rows the merged list of detect_image_tiled keeps at most (60 bytes each, and
+# the merge step's workspace grows with it); later rows are dropped
+TILE_MERGE_ROWS = 1 << 17
+
+
+def detect_image_tiled(net, image, cfg, tile=(1024, 1024), overlap=128, batch=8, border=1.0,
+                       full_pass=True, merge="nms", confidence=0.5, nms_iou=0.3,
+                       vote_thres=0.4, min_votes=1, max_out=750, device="cuda",
+                       nms_kind="greedynms", beta1=1.0, top_k=0, _merged_hook=None):
+    """Sliced detection of a large image, on the device.  image: RGB HWC array,
+    uint8 (uploaded as uint8) or float32.  The image is cut into overlapping
+    tiles (tile_plan(ih, iw, tile, overlap)); the tiles go through the network
+    in chunks of `batch` (ops.tile_gather -> forward -> ops.detect with
+    `confidence`, `nms_iou`, `nms_kind`, `beta1`, `top_k`), the last chunk
+    padded to `batch` slots, so one HIP graph of the shape (batch, 3, th, tw)
+    serves every chunk and every later image whatever its size.  Each chunk's
+    rows join one merged list in image pixels (ops.tile_collect): a box within
+    `border` tile pixels of a tile side inside the image is dropped there (the
+    tile cut the face; the overlap lets a neighbour see it whole).  With
+    `full_pass`, the whole image letterboxed to one tile joins the list as the
+    last pass (ops.tta_collect): it finds the faces larger than the overlap,
+    which every tile cut.  The list is then merged across tiles: merge="nms"
+    runs ops.batched_nms with `nms_iou` and the rule of `nms_kind` / `beta1` on
+    the pixel rows, merge="vote" ops.box_vote (`vote_thres`, pixel +1,
+    `min_votes`); at most max_out rows are returned.  nms_kind "softnms" raises
+    ValueError: decayed scores from different tiles do not compose.  The merged
+    list keeps at most TILE_MERGE_ROWS rows.  Returns numpy float32 [K, 15] in
+    image pixels, descending score; [] when nothing survives.  The call
+    synchronises with the device once, reading the number of result rows
+    (max_out <= 0: once more for the rows).  _merged_hook(merged, offsets), if
+    given, sees the device buffers just before the merge (offsets[-1] rows are
+    valid; offsets[c + 1] closes chunk c, the last entry the full pass)."""
+    if ops.is_soft_kind(nms_kind):
+        raise ValueError("detect_image_tiled: nms_kind 'softnms' is not supported: decayed "
+                         "scores from different tiles do not compose")
+    kind = ops._kind_code(nms_kind, beta1)
+    if merge not in ("nms", "vote"):
+        raise ValueError(f"detect_image_tiled: merge must be 'nms' or 'vote', got {merge!r}")
+    if merge == "vote":
+        ops._vote_args(vote_thres, 1.0, min_votes)
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f"detect_image_tiled: batch must be at least 1, got {batch}")
+    th, tw = _pair("tile", tile)
+    arr = np.asarray(image)
+    if arr.dtype != np.uint8:
+        arr = np.asarray(arr, np.float32)
+    if arr.ndim != 3 or arr.shape[2] != 3:
+        raise ValueError(f"detect_image_tiled: image must be [H, W, 3], got {arr.shape}")
+    ih, iw = int(arr.shape[0]), int(arr.shape[1])
+    plan = tile_plan(ih, iw, (th, tw), overlap)
+    T = plan.shape[0]
+    n_chunks = -(-T // batch)
+    # every chunk gathers `batch` tiles: the padding repeats the last origin
+    padded = np.concatenate([plan, np.repeat(plan[-1:], n_chunks * batch - T, 0)])
+    img = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+    origins = torch.from_numpy(padded).to(device)
+    mean = (104.0, 117.0, 123.0)
+    priors = _priors_for(net, cfg, th, tw, device)
+    A = priors.shape[0]
+    n_pass = n_chunks + (1 if full_pass else 0)
+    cap = max(1, min((T + (1 if full_pass else 0)) * A, TILE_MERGE_ROWS))
+    graph = _use_graph(net, (th, tw, str(device)), True)
+
+    def run(x):
+        if graph:
+            return graphed_detect(net, x, priors, cfg["variance"], confidence, nms_iou,
+                                  nms_kind, beta1, top_k)
+        with F.split_k():
+            loc, conf, landm = net(x)
+        return ops.detect(loc, conf, landm, priors, cfg["variance"], confidence, nms_iou,
+                          nms_kind=nms_kind, beta1=beta1, top_k=top_k)
+    with torch.no_grad():
+        merged = torch.empty((cap, 15), dtype=torch.float32, device=img.device)
+        offsets = torch.zeros(n_pass + 1, dtype=torch.int64, device=img.device)
+        for c in range(n_chunks):
+            org = origins[c * batch:(c + 1) * batch]
+            rows, n_keep = run(ops.tile_gather(img, org, (th, tw), fill=84.0, mean=mean))
+            ops.tile_collect(rows, n_keep, org[:min(batch, T - c * batch)], merged, offsets, c,
+                             (th, tw), (ih, iw), border=border)
+        if full_pass:
+            rows, n_keep = run(ops.letterbox(img.float(), (tw, th), mean=mean))
+            ops.tta_collect(rows[0], n_keep, merged, offsets, n_chunks, (th, tw), (ih, iw),
+                            letterbox=True, flip=False)
+        if _merged_hook is not None:
+            _merged_hook(merged, offsets)
+        bound = min(int(max_out), cap) if max_out > 0 else cap
+        if merge == "vote":
+            out, n_out, _, _ = ops.box_vote(merged.unsqueeze(0), vote_threshold=vote_thres,
+                                            offset=1.0, min_votes=min_votes, max_out=max_out,
+                                            n_valid=offsets[n_pass:])
+            out = out[0, :bound]
+        else:
+            keep, n_out = ops.batched_nms(merged.unsqueeze(0),
+                                          merged[:, 4].contiguous().unsqueeze(0), nms_iou,
+                                          n_valid=offsets[n_pass:], kind=nms_kind,
+                                          beta1=beta1 if kind else 1.0)
+            # entries of keep beyond n_out are not written: any valid row stands in
+            out = merged.index_select(0, keep[0, :bound].clamp_(0, cap - 1))
+        if max_out > 0:
+            # the rows that can be asked for travel with the count: one synchronisation
+            host = torch.empty((bound, 15), dtype=torch.float32, pin_memory=True)
+            host.copy_(out, non_blocking=True)
+            k = min(int(n_out[0].item()), bound)
+            return host[:k].numpy().copy() if k else []
+        k = int(n_out[0].item())
+        if k == 0:
+            return []
+        return out[:k].cpu().numpy()
+
+
+def _priors_key(cfg, H, W, device):
+    return (H, W, str(device), repr(cfg.get("min_sizes")), repr(cfg.get("steps")),
+            bool(cfg.get("clip", False)))
+
+
 def _cached_priors(net, cfg, H, W, device, priors):
     """One priors tensor per (input size, device, anchor cfg) on the module
     (the graph keys on its storage).  The priors are a function of exactly
     these keys (utils/anchors.py:8-42), so another cfg on the same net gets
     its own tensor (and graph) instead of stale priors."""
     cache = net.__dict__.setdefault("_jabd_priors", {})
-    key = (H, W, str(device), repr(cfg.get("min_sizes")), repr(cfg.get("steps")),
-           bool(cfg.get("clip", False)))
+    key = _priors_key(cfg, H, W, device)
     p = cache.get(key)
     if p is None or p.shape != priors.shape:
         p = cache[key] = priors
+    return p
+
+
+def _priors_for(net, cfg, H, W, device):
+    """_cached_priors for a shape that recurs by construction (the tile): the
+    anchors are generated once per key, not per call."""
+    p = net.__dict__.setdefault("_jabd_priors", {}).get(_priors_key(cfg, H, W, device))
+    if p is None:
+        from utils.anchors import Anchors
+        p = Anchors(cfg, image_size=(H, W)).get_anchors().to(device).float().contiguous()
+        p = _cached_priors(net, cfg, H, W, device, p)
     return p
