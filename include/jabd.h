@@ -126,7 +126,15 @@ int jabd_batched_nms_ex_f32(const float* boxes, int64_t box_stride,
  * number of exact IoU (or DIoU) tests made by
  * the grid producer (candidate pairs), its off-block suppressing pairs, and
  * its producer (0 = grid, != 0 = dense: every pair tested).  Synchronises
- * the stream; batch <= 254. */
+ * the stream; batch <= 254.  Fails (JABD_EINVAL) if the grid images' scan
+ * reported a timed-out staging hand-off.
+ * The producer word is an OR of the reasons the image left the grid producer:
+ *   1  NaN boxes (a call that runs no grid producer at all -- a negative
+ *      threshold, n at most the dense-rows limit -- fills 1 for every image)
+ *   2  a box's cell index out of range (beyond +-2^14 cells of its class)
+ *   4  pair capacity exhausted (more off-block pairs than the workspace holds)
+ *   8  at most JABD_NMS_DENSE_MAX candidates (default 8192) after the score
+ *      filter, n_valid and top_k */
 int jabd_nms_pair_stats(const void* ws, size_t ws_bytes, int64_t batch, int64_t n,
                         int64_t* tested, int32_t* hits, int32_t* dense, jabd_stream_t stream);
 

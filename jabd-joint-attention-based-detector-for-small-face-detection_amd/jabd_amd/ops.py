@@ -129,30 +129,41 @@ def batched_nms(boxes, scores, iou_threshold, score_threshold=-math.inf, n_valid
     return keep, n_keep
 
 
-def batched_nms_stats(boxes, scores, iou_threshold, kind="iou", beta1=1.0):
-    """batched_nms plus per-image measurement counters: (keep, n_keep,
-    tested int64[B], dense bool[B]) where `tested` is the number of exact
-    fp32 IoU (or DIoU) evaluations the mask producer made (grid: its candidate
-    pairs; dense: every pair).  Synchronises (measurement only)."""
+def batched_nms_stats(boxes, scores, iou_threshold, score_threshold=-math.inf, n_valid=None,
+                      kind="iou", beta1=1.0, top_k=0, return_flags=False):
+    """batched_nms (same arguments, same C call) plus per-image measurement
+    counters: (keep, n_keep, tested int64[B], dense bool[B]) where `tested` is
+    the number of exact fp32 IoU (or DIoU) evaluations the mask producer made
+    (grid: its candidate pairs; dense: every pair).  return_flags: the fourth
+    result is the producer word itself, int32[B] (0 = grid; the bits are listed
+    at jabd_nms_pair_stats in include/jabd.h) instead of `word != 0`.  Raises
+    if the pull scan's staging hand-off timed out.  Synchronises (measurement
+    only); B <= 254."""
     k = _kind_code(kind, beta1)
+    if boxes.dim() != 3 or boxes.shape[-1] < 4:
+        raise ValueError(f"batched_nms_stats: boxes must be [B,N,>=4], got {tuple(boxes.shape)}")
     B, N = boxes.shape[0], boxes.shape[1]
     dev = boxes.device
     boxes = _dev("nms.boxes", boxes)
     scores = _dev("nms.scores", scores)
+    if scores.shape != (B, N):
+        raise ValueError(f"batched_nms_stats: scores {tuple(scores.shape)} != {(B, N)}")
     keep = torch.empty((B, N), dtype=torch.int64, device=dev)
     n_keep = torch.zeros((B,), dtype=torch.int64, device=dev)
+    if n_valid is not None:
+        n_valid = _dev("nms.n_valid", n_valid, torch.int64)
     ws = _ws(_size_query("jabd_nms_workspace_size", B, N), dev)
     C = boxes.shape[-1]
-    _nms_call(k, beta1, 0, _p(boxes), C, N * C, _p(scores), 1, N, None, B, N,
-              float(iou_threshold), float(-math.inf), _p(keep), _p(n_keep), _p(ws), ws.numel(),
-              _stream())
+    _nms_call(k, beta1, top_k, _p(boxes), C, N * C, _p(scores), 1, N, _p(n_valid), B, N,
+              float(iou_threshold), float(score_threshold), _p(keep), _p(n_keep), _p(ws),
+              ws.numel(), _stream())
     tested = np.zeros(B, np.int64)
     hits = np.zeros(B, np.int32)
     dense = np.zeros(B, np.int32)
     call("jabd_nms_pair_stats", _p(ws), ws.numel(), B, N, tested.ctypes.data, hits.ctypes.data,
          dense.ctypes.data, _stream())
     tested = np.where(dense != 0, N * (N - 1) // 2, tested)
-    return keep, n_keep, tested, dense != 0
+    return keep, n_keep, tested, dense if return_flags else dense != 0
 
 
 def nms(boxes, scores, iou_threshold):
