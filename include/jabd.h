@@ -388,6 +388,65 @@ int jabd_tile_collect_f32(const float* rows, const int64_t* n_keep, int64_t n_ti
                           size_t ws_bytes, jabd_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * Batched detection of images of different sizes: every image is letterboxed
+ * to the one fixed network input, the batch runs through the fixed-shape
+ * forward and jabd_detect, and each slot's rows come back in its own image's
+ * pixels, packed for one download.  Both calls read one slot table:
+ *   desc     device int64 [n, 3] = (byte offset into pool, ih, iw).
+ * With nw = int(iw * s), nh = int(ih * s), s = min(w / iw, h / ih) as
+ * jabd_letterbox_f32 derives them, a slot is EMPTY when ih <= 0 or iw <= 0
+ * (or either exceeds INT32_MAX), or nw == 0 or nh == 0, or (letterbox only)
+ * its bytes [offset, offset + 3 * ih * iw) do not lie inside [0, pool_bytes).
+ *
+ * jabd_letterbox_batch_u8: the ragged letterbox.
+ *   pool     device bytes: the images' RGB HWC uint8 data back to back; no
+ *            alignment is required of an image's start.
+ *   dst      device float32 [n, 3, h, w], 16-byte aligned.  dst[i] holds the
+ *            bytes jabd_letterbox_f32(nchw = 1) gives for image i converted to
+ *            float32 (the conversion is exact): the same nw, nh, top, left and
+ *            tap scales, derived on the device in double from desc, the same
+ *            exact-2x INTER_AREA switch and tap arithmetic.  An empty slot's
+ *            canvas is fill - mean3[c] everywhere and nothing is read from
+ *            pool for it: a padded batch relies on this, and the range clause
+ *            keeps a bad table from reading outside the allocation.
+ *   mean3    host float[3].
+ * n == 0 launches nothing; n <= 65535.  One launch: one thread makes four
+ * consecutive canvas pixels of a row and writes three 16-byte plane stores
+ * (launch tag 4; a w that is no multiple of 4 takes the one-pixel form, tag
+ * 1).  n * h * w * 12 bytes written, at most 12 source bytes read per canvas
+ * pixel inside the image.
+ *
+ * jabd_batch_collect_f32: per-image box correction and packing.
+ *   rows     device float32 [n_slots >= n, A, 15], jabd_detect's output in
+ *            normalised canvas coordinates; n_keep device int64 [n_slots].
+ *            Only the first n slots are read.
+ *   count_i  = clamp(n_keep[i], 0, A), cut to max_det when max_det > 0, and 0
+ *            for an empty slot.
+ *   offsets  device int64 [n + 1]: the call writes offsets[0] = 0 and
+ *            offsets[i + 1] = min(offsets[i] + count_i, cap).
+ *   out      device float32 [cap, 15]: row r < count_i of slot i lands at
+ *            out[offsets[i] + r]; rows at or beyond cap are dropped (the
+ *            contract, not an error).  Every coordinate column goes through
+ *            the arithmetic of jabd_correct_boxes_f32(letterbox = 1,
+ *            to_pixels = 1) with the input shape (input_h, input_w) and image
+ *            i's (ih, iw), the per-image terms derived on the device in
+ *            double; column 4 (score) is copied bit for bit.  Rows of out no
+ *            survivor lands on are not written.
+ * One launch, no atomics (every workgroup sums the counts before its slot in
+ * the same order: two runs give identical bytes), no memset, no host
+ * synchronisation: the call can be captured in a HIP graph.  n == 0 writes
+ * only offsets[0].  n <= 4096, A * 15 < 2^31.
+ * ------------------------------------------------------------------------ */
+int jabd_letterbox_batch_u8(const uint8_t* pool, int64_t pool_bytes,
+                            const int64_t* desc, int64_t n, float* dst, int h,
+                            int w, float fill, const float* mean3,
+                            jabd_stream_t stream);
+int jabd_batch_collect_f32(const float* rows, const int64_t* n_keep, int64_t n,
+                           int64_t A, const int64_t* desc, int input_h,
+                           int input_w, int64_t max_det, float* out,
+                           int64_t cap, int64_t* offsets, jabd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * A7/A8 anchor matching + encoding — nets/retinaface_training.py:93-162
  * (match/encode/encode_landm) for a whole batch in one pass.
  *   targets  [T, 15] device fp32: the B per-image target tensors concatenated

@@ -814,6 +814,62 @@ __device__ __forceinline__ void lin_tap(int d, double scale, int n, int& s0, int
   f = fx;
 }
 
+// The geometry of one letterbox: utils/utils.py:10-13 (scale = min(w/iw,
+// h/ih); nw = int(iw*scale); nh = int(ih*scale), numpy float64) and cv2.resize's
+// inv_scale = dsize/ssize, scale = 1/inv_scale; an exact 2x is INTER_AREA.
+// ih, iw, h, w > 0.  Host and device evaluate the same IEEE double expressions.
+struct LetterboxGeom {
+  int nw, nh, top, left, area2x;
+  double sx, sy;
+};
+
+__host__ __device__ inline LetterboxGeom letterbox_geom(int ih, int iw, int h, int w) {
+  LetterboxGeom g;
+  const double sc = fmin((double)w / iw, (double)h / ih);
+  g.nw = (int)(iw * sc);
+  g.nh = (int)(ih * sc);
+  g.top = (h - g.nh) / 2;
+  g.left = (w - g.nw) / 2;
+  g.sx = 1.0 / ((double)g.nw / iw);  // inf when the side collapses: the callers reject it first
+  g.sy = 1.0 / ((double)g.nh / ih);
+  g.area2x = (iw == 2 * g.nw && ih == 2 * g.nh) ? 1 : 0;
+  return g;
+}
+
+__device__ __forceinline__ float letterbox_px(const float* p) { return *p; }
+__device__ __forceinline__ float letterbox_px(const uint8_t* p) { return (float)*p; }
+
+// pixel (ry, rx) of the resized nw x nh image, 0 <= ry < nh, 0 <= rx < nw
+template <typename T>
+__device__ __forceinline__ void letterbox_sample(const T* __restrict__ S, int ih, int iw, int ry,
+                                                 int rx, double sx, double sy, int area2x,
+                                                 float* v) {
+  if (area2x) {
+    const T* r0 = S + ((int64_t)(2 * ry) * iw + 2 * rx) * 3;
+    const T* r1 = r0 + (int64_t)iw * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      v[c] = (letterbox_px(r0 + c) + letterbox_px(r0 + c + 3) + letterbox_px(r1 + c) +
+              letterbox_px(r1 + c + 3)) * 0.25f;
+  } else {
+    int x0, x1, y0, y1;
+    float fx, fy;
+    lin_tap(rx, sx, iw, x0, x1, fx);
+    lin_tap(ry, sy, ih, y0, y1, fy);
+    const float ax0 = 1.f - fx, ay0 = 1.f - fy;
+    const T* p00 = S + ((int64_t)y0 * iw + x0) * 3;
+    const T* p01 = S + ((int64_t)y0 * iw + x1) * 3;
+    const T* p10 = S + ((int64_t)y1 * iw + x0) * 3;
+    const T* p11 = S + ((int64_t)y1 * iw + x1) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float h0 = letterbox_px(p00 + c) * ax0 + letterbox_px(p01 + c) * fx;
+      const float h1 = letterbox_px(p10 + c) * ax0 + letterbox_px(p11 + c) * fx;
+      v[c] = h0 * ay0 + h1 * fy;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void letterbox_kernel(
     const float* __restrict__ src, int ih, int iw, float* __restrict__ dst, int h, int w,
     int nw, int nh, int top, int left, double sx, double sy, int area2x, float fill, float m0,
@@ -825,30 +881,8 @@ __global__ __launch_bounds__(256) void letterbox_kernel(
   const float* S = src + (int64_t)b * ih * iw * 3;
   float v[3] = {fill, fill, fill};
   const int ry = y - top, rx = x - left;
-  if (ry >= 0 && ry < nh && rx >= 0 && rx < nw) {
-    if (area2x) {
-      const float* r0 = S + ((int64_t)(2 * ry) * iw + 2 * rx) * 3;
-      const float* r1 = r0 + (int64_t)iw * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = (r0[c] + r0[c + 3] + r1[c] + r1[c + 3]) * 0.25f;
-    } else {
-      int x0, x1, y0, y1;
-      float fx, fy;
-      lin_tap(rx, sx, iw, x0, x1, fx);
-      lin_tap(ry, sy, ih, y0, y1, fy);
-      const float ax0 = 1.f - fx, ay0 = 1.f - fy;
-      const float* p00 = S + ((int64_t)y0 * iw + x0) * 3;
-      const float* p01 = S + ((int64_t)y0 * iw + x1) * 3;
-      const float* p10 = S + ((int64_t)y1 * iw + x0) * 3;
-      const float* p11 = S + ((int64_t)y1 * iw + x1) * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float h0 = p00[c] * ax0 + p01[c] * fx;
-        const float h1 = p10[c] * ax0 + p11[c] * fx;
-        v[c] = h0 * ay0 + h1 * fy;
-      }
-    }
-  }
+  if (ry >= 0 && ry < nh && rx >= 0 && rx < nw)
+    letterbox_sample(S, ih, iw, ry, rx, sx, sy, area2x, v);
   if (nchw) {
     float* D = dst + (int64_t)b * 3 * h * w + pix;
     const int64_t plane = (int64_t)h * w;
@@ -922,8 +956,8 @@ __global__ void tta_collect_kernel(const float* __restrict__ rows,
 }
 
 // utils_bbox.py:10-12, numpy float64 over [h, w] pairs
-static CorrectArgs correct_args(int input_h, int input_w, int image_h, int image_w,
-                                int letterbox, int to_pixels) {
+__host__ __device__ static CorrectArgs correct_args(int input_h, int input_w, int image_h,
+                                                    int image_w, int letterbox, int to_pixels) {
   CorrectArgs a{letterbox, 0, 0, 1, 1, to_pixels ? (double)image_w : 1.0,
                 to_pixels ? (double)image_h : 1.0};
   if (letterbox) {
@@ -935,6 +969,155 @@ static CorrectArgs correct_args(int input_h, int input_w, int image_h, int image
     a.scx = input_w / nw;
   }
   return a;
+}
+
+// ---------------------------------------------------------------------------
+// Batched detection of images of different sizes (predict.detect_images): the
+// ragged letterbox in front of the fixed-shape forward and the per-image box
+// correction + packing behind it.  Semantics: jabd_letterbox_batch_u8 and
+// jabd_batch_collect_f32 in include/jabd.h.  Both read the slot table desc
+// [n, 3] = (byte offset into the pool, ih, iw) on the device; blockIdx.y is the
+// slot, so a workgroup's image is uniform and its geometry is derived once, in
+// double, with the host expressions of jabd_letterbox_f32 / correct_args.
+//
+// letterbox_batch: letterbox_kernel's arithmetic (letterbox_sample) on uint8
+// sources, NCHW output.  One thread per four canvas pixels of a row, three
+// 16-byte plane stores (a w that is no multiple of 4: one pixel per thread);
+// the four pixels are sampled one by one, so a group may straddle the
+// bar / image boundary.  Memory-bound: 12 bytes written per canvas pixel, at
+// most 4 taps x 3 source bytes read; the LDS holds the geometry record only.
+//
+// batch_collect: one launch, one thread per (row, column) of a slot.  Every
+// workgroup sums the counts of the slots before its own (integers, every
+// workgroup in the same order: the position is a function of the data alone);
+// no atomics, no memset, two runs give identical bytes.
+// ---------------------------------------------------------------------------
+static constexpr int kBatchT = 256;
+static constexpr int kBatchWaves = kBatchT / 64;
+
+// Slot i of the table: its (ih, iw) and letterbox to h x w.  False for an empty
+// slot: a side <= 0 or beyond int, or a letterbox that collapses (nw or nh 0).
+__device__ __forceinline__ bool batch_slot(const int64_t* __restrict__ desc, int64_t i, int h,
+                                           int w, int& ih, int& iw, LetterboxGeom& g) {
+  const int64_t a = desc[3 * i + 1], b = desc[3 * i + 2];
+  if (a <= 0 || b <= 0 || a > 0x7fffffff || b > 0x7fffffff) return false;
+  ih = (int)a;
+  iw = (int)b;
+  g = letterbox_geom(ih, iw, h, w);
+  return g.nw > 0 && g.nh > 0;
+}
+
+struct BatchSlot {
+  const uint8_t* src;
+  int ih, iw, empty;
+  LetterboxGeom g;
+};
+
+// VEC = 4: w % 4 == 0, one thread per 4 pixels; VEC = 1: any w
+template <int VEC>
+__global__ __launch_bounds__(kBatchT) void letterbox_batch_kernel(
+    const uint8_t* __restrict__ pool, int64_t pool_bytes, const int64_t* __restrict__ desc,
+    float* __restrict__ dst, int h, int w, float fill, float m0, float m1, float m2) {
+  __shared__ BatchSlot slot;
+  const int b = blockIdx.y;
+  if (threadIdx.x == 0) {
+    BatchSlot s{pool, 0, 0, 1, LetterboxGeom{0, 0, 0, 0, 0, 1.0, 1.0}};
+    int ih, iw;
+    LetterboxGeom g;
+    if (batch_slot(desc, b, h, w, ih, iw, g)) {
+      const int64_t off = desc[3 * b];
+      // the range guard, 3 * ih * iw <= pool_bytes - off without overflow
+      if (off >= 0 && off <= pool_bytes && (int64_t)ih * iw <= (pool_bytes - off) / 3)
+        s = BatchSlot{pool + off, ih, iw, 0, g};
+    }
+    slot = s;
+  }
+  __syncthreads();
+  const int wq = w / VEC;
+  const int64_t i = blockIdx.x * (int64_t)kBatchT + threadIdx.x;
+  if (i >= (int64_t)h * wq) return;
+  const int y = (int)(i / wq);
+  const int x = (int)(i - (int64_t)y * wq) * VEC;
+  const uint8_t* S = slot.src;
+  const int ih = slot.ih, iw = slot.iw;
+  const LetterboxGeom g = slot.g;
+  const int ry = y - g.top;
+  const bool yin = !slot.empty && ry >= 0 && ry < g.nh;  // an empty slot reads nothing
+  float v[VEC][3];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    v[k][0] = v[k][1] = v[k][2] = fill;
+    const int rx = x + k - g.left;
+    if (yin && rx >= 0 && rx < g.nw) letterbox_sample(S, ih, iw, ry, rx, g.sx, g.sy, g.area2x, v[k]);
+  }
+  const int64_t plane = (int64_t)h * w;
+  float* D = dst + (int64_t)b * 3 * plane + (int64_t)y * w + x;
+  if constexpr (VEC == 4) {
+    *reinterpret_cast<float4*>(D) =
+        make_float4(v[0][0] - m0, v[1][0] - m0, v[2][0] - m0, v[3][0] - m0);
+    *reinterpret_cast<float4*>(D + plane) =
+        make_float4(v[0][1] - m1, v[1][1] - m1, v[2][1] - m1, v[3][1] - m1);
+    *reinterpret_cast<float4*>(D + 2 * plane) =
+        make_float4(v[0][2] - m2, v[1][2] - m2, v[2][2] - m2, v[3][2] - m2);
+  } else {
+    D[0] = v[0][0] - m0;
+    D[plane] = v[0][1] - m1;
+    D[2 * plane] = v[0][2] - m2;
+  }
+}
+
+// rows slot i contributes: clamp(n_keep[i], 0, A), cut to max_det > 0; 0 when empty
+__device__ __forceinline__ int64_t batch_count(const int64_t* __restrict__ n_keep,
+                                               const int64_t* __restrict__ desc, int64_t i,
+                                               int64_t A, int h, int w, int64_t max_det, int& ih,
+                                               int& iw) {
+  LetterboxGeom g;
+  if (!batch_slot(desc, i, h, w, ih, iw, g)) return 0;
+  int64_t c = n_keep[i];
+  c = c < 0 ? 0 : (c > A ? A : c);
+  return (max_det > 0 && c > max_det) ? max_det : c;
+}
+
+__global__ __launch_bounds__(kBatchT) void batch_collect_kernel(
+    const float* __restrict__ rows, const int64_t* __restrict__ n_keep, int64_t A,
+    const int64_t* __restrict__ desc, int h, int w, int64_t max_det, float* __restrict__ out,
+    int64_t cap, int64_t* __restrict__ offsets) {
+  __shared__ long long wave_sum[kBatchWaves];
+  __shared__ CorrectArgs args;
+  const int t = blockIdx.y, tid = threadIdx.x;
+  int ih = 1, iw = 1, qh, qw;
+  const int64_t cnt = batch_count(n_keep, desc, t, A, h, w, max_det, ih, iw);
+  // a slot's first workgroup stays: it writes offsets[t + 1]
+  if (blockIdx.x > 0 && blockIdx.x * (int64_t)kBatchT >= cnt * 15) return;  // uniform
+  long long s = 0;  // rows of the slots before this one
+  for (int q = tid; q < t; q += kBatchT) s += batch_count(n_keep, desc, q, A, h, w, max_det, qh, qw);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((tid & 63) == 0) wave_sum[tid >> 6] = s;
+  if (tid == 0) args = correct_args(h, w, ih, iw, 1, 1);  // read only when cnt > 0
+  __syncthreads();
+  long long before = 0;
+#pragma unroll
+  for (int q = 0; q < kBatchWaves; ++q) before += wave_sum[q];
+  if (blockIdx.x == 0 && tid == 0) {  // slots no thread reads
+    if (t == 0) offsets[0] = 0;
+    const int64_t end = before + cnt;
+    offsets[t + 1] = end < cap ? end : cap;
+  }
+  const int64_t i = blockIdx.x * (int64_t)kBatchT + tid;
+  const int64_t r = i / 15;
+  const int c = (int)(i - r * 15);
+  if (r >= cnt) return;
+  const int64_t d = before + r;
+  if (d >= cap) return;
+  const float v = rows[((int64_t)t * A + r) * 15 + c];
+  const CorrectArgs a = args;
+  out[d * 15 + c] = c == 4 ? v : correct_value(v, c, a);
+}
+
+// no slots: offsets[0] is all there is to write
+__global__ void batch_collect_empty_kernel(int64_t* __restrict__ offsets) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) offsets[0] = 0;
 }
 
 }  // namespace jabd
@@ -978,21 +1161,62 @@ extern "C" int jabd_letterbox_f32(const float* src, int64_t batch, int ih, int i
   JABD_REQUIRE(!nchw || mean3, "letterbox: NCHW output needs the channel means");
   if (batch == 0) return JABD_OK;
   JABD_REQUIRE(src && dst, "letterbox: null pointer");
-  // utils/utils.py:10-13: scale = min(w/iw, h/ih); nw = int(iw*scale); nh = int(ih*scale)
-  const double sc = fmin((double)w / iw, (double)h / ih);
-  const int nw = (int)(iw * sc), nh = (int)(ih * sc);
-  JABD_REQUIRE(nw > 0 && nh > 0, "letterbox: image %dx%d collapses to %dx%d", iw, ih, nw, nh);
-  const int top = (h - nh) / 2, left = (w - nw) / 2;
-  // cv2.resize: inv_scale = dsize/ssize, scale = 1/inv_scale; exact 2x -> INTER_AREA
-  const double sx = 1.0 / ((double)nw / iw), sy = 1.0 / ((double)nh / ih);
-  const int area2x = (iw == 2 * nw && ih == 2 * nh) ? 1 : 0;
+  const LetterboxGeom lg = letterbox_geom(ih, iw, h, w);
+  JABD_REQUIRE(lg.nw > 0 && lg.nh > 0, "letterbox: image %dx%d collapses to %dx%d", iw, ih,
+               lg.nw, lg.nh);
   const float m[3] = {nchw ? mean3[0] : 0.f, nchw ? mean3[1] : 0.f, nchw ? mean3[2] : 0.f};
   const int64_t npix = (int64_t)h * w;
   dim3 g((unsigned)cdiv(npix, 256), (unsigned)batch);
-  letterbox_kernel<<<g, 256, 0, as_stream(stream)>>>(src, ih, iw, dst, h, w, nw, nh, top, left,
-                                                      sx, sy, area2x, fill, m[0], m[1], m[2],
-                                                      nchw);
+  letterbox_kernel<<<g, 256, 0, as_stream(stream)>>>(src, ih, iw, dst, h, w, lg.nw, lg.nh, lg.top,
+                                                      lg.left, lg.sx, lg.sy, lg.area2x, fill,
+                                                      m[0], m[1], m[2], nchw);
   return check_launch("letterbox");
+}
+
+extern "C" int jabd_letterbox_batch_u8(const uint8_t* pool, int64_t pool_bytes,
+                                       const int64_t* desc, int64_t n, float* dst, int h, int w,
+                                       float fill, const float* mean3, jabd_stream_t stream) {
+  JABD_REQUIRE(n >= 0 && pool_bytes >= 0 && h > 0 && w > 0, "letterbox_batch: bad size");
+  JABD_REQUIRE(mean3, "letterbox_batch: null channel means");
+  if (n == 0) return JABD_OK;
+  JABD_REQUIRE(n <= 65535, "letterbox_batch: n=%lld exceeds 65535 per call", (long long)n);
+  JABD_REQUIRE(desc && dst && (pool || pool_bytes == 0), "letterbox_batch: null pointer");
+  JABD_REQUIRE(((uintptr_t)dst & 15u) == 0, "letterbox_batch: dst must be 16-byte aligned");
+  const bool vec = w % 4 == 0;
+  const int64_t blocks = cdiv((int64_t)h * (vec ? w / 4 : w), kBatchT);
+  JABD_REQUIRE(blocks <= 0x7fffffff, "letterbox_batch: canvas %dx%d too large", w, h);
+  const dim3 g((unsigned)blocks, (unsigned)n);
+  hipStream_t st = as_stream(stream);
+  if (vec) {
+    letterbox_batch_kernel<4><<<g, kBatchT, 0, st>>>(pool, pool_bytes, desc, dst, h, w, fill,
+                                                     mean3[0], mean3[1], mean3[2]);
+    return check_launch("letterbox_batch", 4);
+  }
+  letterbox_batch_kernel<1><<<g, kBatchT, 0, st>>>(pool, pool_bytes, desc, dst, h, w, fill,
+                                                   mean3[0], mean3[1], mean3[2]);
+  return check_launch("letterbox_batch", 1);
+}
+
+extern "C" int jabd_batch_collect_f32(const float* rows, const int64_t* n_keep, int64_t n,
+                                      int64_t A, const int64_t* desc, int input_h, int input_w,
+                                      int64_t max_det, float* out, int64_t cap,
+                                      int64_t* offsets, jabd_stream_t stream) {
+  JABD_REQUIRE(n >= 0 && A >= 0 && cap >= 0, "batch_collect: bad size");
+  JABD_REQUIRE(input_h > 0 && input_w > 0, "batch_collect: bad input shape");
+  JABD_REQUIRE(n <= 4096, "batch_collect: n=%lld exceeds 4096 per call", (long long)n);
+  JABD_REQUIRE(A * 15 < (int64_t(1) << 31), "batch_collect: A=%lld too large", (long long)A);
+  JABD_REQUIRE(offsets, "batch_collect: null offsets");
+  JABD_REQUIRE(n == 0 || (n_keep && desc && (rows || A == 0)), "batch_collect: null pointer");
+  JABD_REQUIRE(out || cap == 0, "batch_collect: null out");
+  hipStream_t st = as_stream(stream);
+  if (n == 0) {
+    batch_collect_empty_kernel<<<1, 64, 0, st>>>(offsets);
+    return check_launch("batch_collect_empty");
+  }
+  const int64_t bx = cdiv(A * 15, kBatchT);
+  batch_collect_kernel<<<dim3((unsigned)(bx < 1 ? 1 : bx), (unsigned)n), kBatchT, 0, st>>>(
+      rows, n_keep, A, desc, input_h, input_w, max_det, out, cap, offsets);
+  return check_launch("batch_collect");
 }
 
 extern "C" int jabd_decode_f32(const float* loc, const float* priors, int64_t batch,

@@ -401,6 +401,141 @@ def tile_collect(rows, n_keep, origins, merged, offsets, pass_index, tile, image
     return merged
 
 
+# --------------------------------------------------------------------------- batched detection
+def _image_u8(name, index, image):
+    """image as a C-contiguous uint8 [H, W, 3] array."""
+    arr = np.asarray(image)
+    if arr.dtype != np.uint8:
+        raise TypeError(f"{name}: image {index} must be uint8, got {arr.dtype}")
+    if arr.ndim != 3 or arr.shape[2] != 3 or arr.shape[0] < 1 or arr.shape[1] < 1:
+        raise ValueError(f"{name}: image {index} must be [H, W, 3], got {arr.shape}")
+    return np.ascontiguousarray(arr)
+
+
+def _letterbox_sides(ih, iw, size):
+    """(nw, nh) of utils/utils.py:10-13 for size = (w, h), as jabd_letterbox_f32
+    derives them (float64)."""
+    w, h = int(size[0]), int(size[1])
+    scale = min(w / iw, h / ih)
+    return int(iw * scale), int(ih * scale)
+
+
+def _pack_arrays(name, images, size, first=0):
+    """The checked uint8 arrays of `images` and their int64 [n, 3] slot table
+    (offsets from 0); `first` is the index of images[0] in the caller's count."""
+    arrs = [_image_u8(name, first + i, im) for i, im in enumerate(images)]
+    desc = np.zeros((len(arrs), 3), np.int64)
+    off = 0
+    for i, a in enumerate(arrs):
+        ih, iw = a.shape[0], a.shape[1]
+        if size is not None:
+            nw, nh = _letterbox_sides(ih, iw, size)
+            if nw == 0 or nh == 0:
+                raise ValueError(f"{name}: image {first + i} ({ih} x {iw}) collapses to "
+                                 f"{nh} x {nw} on a {int(size[1])} x {int(size[0])} canvas")
+        desc[i] = (off, ih, iw)
+        off += a.size
+    return arrs, desc, off
+
+
+def pack_images(images, size=None):
+    """Host only: the pool and slot table ops.letterbox_batch takes.  images:
+    uint8 [H, W, 3] RGB arrays (or anything np.asarray turns into one) of any
+    sizes; another dtype raises TypeError, another shape ValueError.  Returns
+    (pool, desc): pool uint8 1-D, the images' bytes back to back, and desc
+    int64 [n, 3] = (byte offset into pool, ih, iw), both pinned where a device
+    is present (plain host tensors otherwise).  With size = (w, h) an image
+    whose letterbox to that canvas collapses (nw or nh 0) raises ValueError
+    naming its index, before any device work."""
+    arrs, desc, total = _pack_arrays("pack_images", list(images), size)
+    pin = torch.cuda.is_available()
+    pool = torch.empty(total, dtype=torch.uint8, pin_memory=pin)
+    view = pool.numpy()
+    for a, (off, _, _) in zip(arrs, desc):
+        view[off:off + a.size] = a.reshape(-1)
+    table = torch.empty((len(arrs), 3), dtype=torch.int64, pin_memory=pin)
+    table.numpy()[...] = desc
+    return pool, table
+
+
+def _batch_desc(name, desc):
+    desc = _dev(name + ".desc", desc, torch.int64)
+    if desc.dim() != 2 or desc.shape[1] != 3:
+        raise ValueError(f"{name}: desc must be int64 [n, 3], got {tuple(desc.shape)}")
+    return desc
+
+
+def letterbox_batch(pool, desc, size, fill=84.0, mean=(104.0, 117.0, 123.0), pool_bytes=None):
+    """Images of different sizes letterboxed into one network input batch
+    (jabd_letterbox_batch_u8).  pool device uint8 1-D and desc device int64
+    [n, 3] as ops.pack_images lays them out; size = (w, h) as ops.letterbox
+    takes it.  Returns float32 [n, 3, h, w]: slot i holds the bytes of
+    ops.letterbox(image_i.float(), size, fill, mean).  An empty slot (ih or iw
+    <= 0, a letterbox that collapses, or bytes not inside the pool) is
+    fill - mean everywhere and reads nothing.  pool_bytes (default: all of
+    pool) is the size the range check uses; it may not exceed len(pool)."""
+    pool = _dev("letterbox_batch.pool", pool, torch.uint8)
+    if pool.dim() != 1:
+        raise ValueError(f"letterbox_batch: pool must be 1-D, got {tuple(pool.shape)}")
+    desc = _batch_desc("letterbox_batch", desc)
+    w, h = int(size[0]), int(size[1])
+    if w < 1 or h < 1:
+        raise ValueError(f"letterbox_batch: bad size {size!r}")
+    nbytes = pool.numel() if pool_bytes is None else int(pool_bytes)
+    if not 0 <= nbytes <= pool.numel():
+        raise ValueError(f"letterbox_batch: pool_bytes {nbytes} outside [0, {pool.numel()}]")
+    n = desc.shape[0]
+    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=pool.device)
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    call("jabd_letterbox_batch_u8", _p(pool), nbytes, _p(desc), n, _p(out), h, w, float(fill),
+         ctypes.cast(m, ctypes.c_void_p), _stream())
+    return out
+
+
+def batch_collect(rows, n_keep, desc, input_shape, max_det=0, out=None, offsets=None):
+    """A batch's detect rows brought to each image's own pixels and packed
+    (jabd_batch_collect_f32).  rows [n_slots, A, 15] and n_keep [n_slots] are
+    ops.detect's outputs for a letterboxed batch, desc device int64 [n, 3]
+    the batch's slot table (n <= n_slots: only the first n slots are read),
+    input_shape = (H, W) of the network input.  Slot i contributes its first
+    count_i = clamp(n_keep[i], 0, A) rows, at most max_det of them when
+    max_det > 0 and none when the slot is empty; they are corrected as
+    correct_boxes(..., (ih_i, iw_i), letterbox=True, to_pixels=True) and
+    written from out[offsets[i]] on, with offsets[0] = 0 and offsets[i + 1] =
+    min(offsets[i] + count_i, len(out)).  out: device float32 [cap, 15]
+    (default: a new [n * A, 15] tensor; rows beyond the capacity are dropped,
+    rows no survivor lands on are left as they are), offsets: device int64
+    [n + 1] (default: new).  No host synchronisation.  Returns (out, offsets)."""
+    rows = _dev("batch_collect.rows", rows)
+    n_keep = _dev("batch_collect.n_keep", n_keep, torch.int64)
+    desc = _batch_desc("batch_collect", desc)
+    if rows.dim() != 3 or rows.shape[2] != 15:
+        raise ValueError(f"batch_collect: rows must be [n_slots, A, 15], got {tuple(rows.shape)}")
+    S, A = rows.shape[0], rows.shape[1]
+    n = desc.shape[0]
+    if n > S or n_keep.numel() < n:
+        raise ValueError(f"batch_collect: {n} table rows for {S} slots and {n_keep.numel()} "
+                         "counts")
+    H, W = int(input_shape[0]), int(input_shape[1])
+    if H < 1 or W < 1:
+        raise ValueError(f"batch_collect: bad input shape {input_shape!r}")
+    if out is None:
+        out = torch.empty((n * A, 15), dtype=torch.float32, device=rows.device)
+    if offsets is None:
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=rows.device)
+    for name, t, dt in (("out", out, torch.float32), ("offsets", offsets, torch.int64)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt
+                and t.is_contiguous()):
+            raise ValueError(f"batch_collect: {name} must be a contiguous device {dt} tensor")
+    if out.dim() != 2 or out.shape[1] != 15:
+        raise ValueError(f"batch_collect: out must be [cap, 15], got {tuple(out.shape)}")
+    if offsets.dim() != 1 or offsets.numel() < n + 1:
+        raise ValueError(f"batch_collect: offsets needs {n + 1} entries")
+    call("jabd_batch_collect_f32", _p(rows), _p(n_keep), n, A, _p(desc), H, W, int(max_det),
+         _p(out), out.shape[0], _p(offsets), _stream())
+    return out, offsets
+
+
 def detect(loc, conf, landm, priors, variances, conf_threshold=0.5, nms_threshold=0.3,
            nms_kind="greedynms", beta1=1.0, top_k=0, sigma=0.5, soft_offset=0.0):
     """predict.py:162-181 on device for a batch: decode + filter + NMS.

@@ -165,6 +165,128 @@ def detect_image(net, image, input_shape, cfg, confidence=0.5, nms_iou=0.3,
     return det.cpu().numpy()
 
 
+def _pinned(stash, slot, nbytes):
+    """Pinned uint8 buffer `slot` of a call's staging set, grown when too small."""
+    buf = stash.get(slot)
+    if buf is None or buf.numel() < nbytes:
+        buf = stash[slot] = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=True)
+    return buf
+
+
+def detect_images(net, images, input_shape, cfg, batch=8, max_det=750, confidence=0.5,
+                  nms_iou=0.3, device="cuda", nms_kind="greedynms", beta1=1.0, top_k=0,
+                  sigma=0.5, soft_offset=0.0):
+    """detect_image(..., letterbox_image=True) for many images of any sizes at
+    batch throughput: predict.py's dir_predict, video and get_map_txt loops.
+    images: an iterable of RGB HWC uint8 arrays (anything np.asarray turns into
+    one; another dtype raises TypeError, another shape or an image whose
+    letterbox collapses ValueError, before that chunk's device work).  It is
+    consumed `batch` images at a time, so a generator over a folder never holds
+    the folder.  Returns a list with one numpy float32 [K_i, 15] per image, in
+    order: the rows detect_image returns for that image (image pixels, NMS
+    order), cut to the first max_det (max_det <= 0: all).  An image without a
+    detection gives an array of shape (0, 15), not detect_image's [].
+
+    Per chunk: the slot table and the images' bytes go to the device in one
+    non-blocking copy from pinned memory, ops.letterbox_batch fills `batch`
+    slots (the last chunk is padded with empty slots, so one HIP graph of the
+    shape (batch, 3, H, W) serves every chunk and every later call), the
+    forward + ops.detect run as in detect_image, ops.batch_collect brings each
+    slot's rows to its image's pixels, and the offsets with the first
+    min(batch * max_det, batch * A) rows come back in one non-blocking copy
+    followed by an event.  Chunks are pipelined two deep (two staging and two
+    result buffers): chunk c + 1 is packed and enqueued before chunk c's event
+    is waited on, and that wait is the chunk's only host synchronisation
+    (max_det <= 0: one more, for the rows)."""
+    import itertools
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f"detect_images: batch must be at least 1, got {batch}")
+    H, W = _pair("input_shape", input_shape)
+    if H < 1 or W < 1:
+        raise ValueError(f"detect_images: bad input shape {input_shape!r}")
+    if ops.is_soft_kind(nms_kind):
+        ops._soft_args(sigma, soft_offset)
+    else:
+        ops._kind_code(nms_kind, beta1)
+    max_det = max(int(max_det), 0)
+    it = iter(images)
+    head = batch * 24                      # the slot table leads the staging buffer
+    stage, result = {}, {}
+    state = {}
+
+    def setup():
+        priors = _priors_for(net, cfg, H, W, device)
+        A = priors.shape[0]
+        state.update(priors=priors, A=A, cap=batch * (min(max_det, A) if max_det else A),
+                     graph=_use_graph(net, (H, W, str(device)), True))
+
+    def enqueue(chunk, first, slot):
+        arrs, desc, total = ops._pack_arrays("detect_images", chunk, (W, H), first)
+        buf = _pinned(stage, slot, head + total)
+        host = buf.numpy()
+        table = host[:head].view(np.int64).reshape(batch, 3)
+        table[...] = 0                     # the padding: empty slots
+        table[:len(arrs)] = desc
+        for a, (off, _, _) in zip(arrs, desc):
+            host[head + off:head + off + a.size] = a.reshape(-1)
+        if not state:
+            setup()
+        A, cap = state["A"], state["cap"]
+        dev = buf[:head + total].to(device, non_blocking=True)
+        table = dev[:head].view(torch.int64).view(batch, 3)
+        x = ops.letterbox_batch(dev[head:], table, (W, H), fill=84.0,
+                                mean=(104.0, 117.0, 123.0))
+        if state["graph"]:
+            rows, n_keep = graphed_detect(net, x, state["priors"], cfg["variance"], confidence,
+                                          nms_iou, nms_kind, beta1, top_k, sigma, soft_offset)
+        else:
+            with F.split_k():
+                loc, conf, landm = net(x)
+            rows, n_keep = ops.detect(loc, conf, landm, state["priors"], cfg["variance"],
+                                      confidence, nms_iou, nms_kind=nms_kind, beta1=beta1,
+                                      top_k=top_k, sigma=sigma, soft_offset=soft_offset)
+        # offsets and rows share one buffer: one copy brings both back
+        tail = (batch + 1) * 8
+        res = torch.empty(tail + cap * 60, dtype=torch.uint8, device=dev.device)
+        offsets = res[:tail].view(torch.int64)
+        out = res[tail:].view(torch.float32).view(cap, 15)
+        ops.batch_collect(rows, n_keep, table, (H, W), max_det=max_det, out=out, offsets=offsets)
+        back = res if max_det else res[:tail]
+        hres = _pinned(result, slot, back.numel())[:back.numel()]
+        hres.copy_(back, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        return len(arrs), hres, out, done
+
+    def finish(job):
+        n, hres, out, done = job
+        done.synchronize()
+        host = hres.numpy()
+        tail = (batch + 1) * 8
+        offs = host[:tail].view(np.int64)
+        if max_det:
+            rows = host[tail:].view(np.float32).reshape(-1, 15)
+        else:                              # no cap: the rows that exist, one more wait
+            rows = out[:int(offs[n])].cpu().numpy()
+        return [rows[offs[i]:offs[i + 1]].copy() for i in range(n)]
+
+    results, pending, first = [], None, 0
+    with torch.no_grad():
+        for c in itertools.count():
+            chunk = list(itertools.islice(it, batch))
+            if not chunk:
+                break
+            job = enqueue(chunk, first, c & 1)
+            first += len(chunk)
+            if pending is not None:
+                results += finish(pending)
+            pending = job
+        if pending is not None:
+            results += finish(pending)
+    return results
+
+
 def _tta_passes(net, img, cfg, scales, flip, confidence, nms_iou, device, nms_kind, beta1, top_k):
     """The passes of detect_image_tta: (rows [A, 15], n_keep [1], (H, W),
     mirrored) one after the other, each valid until the next is asked for (a
