@@ -46,9 +46,19 @@ __device__ __forceinline__ float cs_act(float v, int act, float slope) {
   }
 }
 
-// KC >= p.Kc stages are compiled; stages past p.Kc issue a load of the last
-// real stage (an L1 hit, keeps the load sequence unpredicated) and skip their
-// MFMAs (wave-uniform branch).
+// FULL: p.Kc == KC, every compiled stage is real and the K loop is one basic
+// block.  !FULL (the rounded instances, KC - 2 <= p.Kc < KC by stream_kc's
+// list): only the last two stages test p.Kc; a stage past p.Kc issues a load
+// of the last real stage (an L1 hit, keeps the load sequence unpredicated)
+// and skips its MFMAs (wave-uniform branch).
+// Within a stage the TN accumulators are interleaved (acc[0..TN) with w.x,
+// then with w.y, ...) so consecutive MFMAs are independent, and the LDS
+// operands roll one stage ahead in a single register set: fragment u of stage
+// kc + 1 is read right behind the last MFMA that uses fragment u of stage kc
+// (TN - 1 MFMAs before its first use), the gate float4 of stage kc + 1 behind
+// the stage's first MFMA group, across the block boundary too.  Per
+// accumulator the order is still bias, then stages in ascending k with
+// x, y, z, w inside a stage.
 // Workgroup: 4 waves; 8 when the weights exceed 24 KiB (Kc x Ntiles > 24: the
 // Cout = 80 layers), so the one workgroup that fits a CU's LDS still gives
 // each SIMD two waves.
@@ -65,30 +75,95 @@ struct CsCfg {
 // with the same MFMA sequence as the real pixel 0 (workgroup 0 stores it to
 // shift[] for bn_stats_final).  Saves bn1's statistics pass over the
 // expanded tensor.
-template <int TN, int KC, int X2, bool AS, bool ST = false>
+template <int TN, int KC, int X2, bool AS, bool ST = false, bool FULL = true>
 __global__ __launch_bounds__((CsCfg<TN, KC>::NW * 64)) void conv1x1_stream_kernel(
     const ConvArgs p, int nblk, int ohw, float* __restrict__ stp, float* __restrict__ shift) {
   constexpr int NW = CsCfg<TN, KC>::NW, NT = NW * 64;
+  // stages from here on can be partial (K % 16 != 0) or, !FULL, past p.Kc
+  constexpr int KTAIL = FULL ? KC - 1 : (KC > 3 ? KC - 3 : 0);
+  constexpr int RSTAGE = KC >= 16 ? KC * 3 / 4 : 0;  // where a block requests its residual
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int Kc = FULL ? KC : p.Kc;
   f32x4* wl = reinterpret_cast<f32x4*>(smem);
-  float4* gl = reinterpret_cast<float4*>(smem + p.Kc * TN * 64 * 4);
+  float4* gl = reinterpret_cast<float4*>(smem + Kc * TN * 64 * 4);
   const int t = threadIdx.x, lane = t & 63, g = lane >> 4, j = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int nwv = gridDim.x * NW;
+  int blk = blockIdx.x * NW + wave;
+  const int M = (int)p.M, Cin = p.Cin, Ktot = p.Cin + (X2 ? p.Cin2 : 0);
+  const int c4n = Cin >> 2;
+  const float* xg = p.x + p.x_c0;
+
+  // one float4 of A: pixel of lane j in block bk, channels 16kc + 4g .. +3
+  auto issue = [&](int bk, int kc) -> float4 {
+    int m = bk * 16 + j;
+    m = m < M ? m : M - 1;
+    const int kq = (FULL || kc < KC - 2 || kc < Kc ? kc : Kc - 1) * 16 + 4 * g;
+    const float* src;
+    if (X2 && kq >= Cin) {
+      const int k2 = kq - Cin < p.Cin2 ? kq - Cin : 0;
+      src = p.x2 + m * p.x2_ps + k2;
+    } else {
+      // only a stage from KTAIL on can reach past Cin; the others keep kq a
+      // constant so it folds into the load's immediate offset
+      src = xg + m * p.x_ps + (!X2 && kc >= KTAIL && kq >= Cin ? 0 : kq);
+    }
+    return *reinterpret_cast<const float4*>(src);
+  };
+
+  // the first block's operands are requested before the weights, so their
+  // HBM latency runs under the staging below
+  float4 bias[TN];
+#pragma unroll
+  for (int u = 0; u < TN; ++u) {
+    const int n0 = 16 * u + 4 * g;
+    bias[u] = p.bias && n0 < p.Cout ? *reinterpret_cast<const float4*>(p.bias + n0)
+                                    : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float4 A[KC];
+#pragma unroll
+  for (int kc = 0; kc < KC; ++kc) A[kc] = issue(blk < nblk ? blk : 0, kc);
   {
+    // every load of a thread is in flight before its first LDS write (loads
+    // past the end re-read the last float4, their writes are dropped)
     const f32x4* ws = reinterpret_cast<const f32x4*>(p.w);
-    const int nw = p.Kc * TN * 64;
-    for (int i = t; i < nw; i += NT) wl[i] = ws[i];
+    const int nw = Kc * TN * 64;
+    constexpr int NI = (KC * TN * 64 + NT - 1) / NT;
+    f32x4 wv[NI];
+#pragma unroll
+    for (int q = 0; q < NI; ++q) {
+      const int i = t + q * NT;
+      wv[q] = ws[i < nw ? i : nw - 1];
+    }
     if (AS) {
-      const int c4n = p.Cin >> 2;
-      for (int i = t; i < p.B * c4n; i += NT) {
-        const int b = i / c4n, c = i - b * c4n;
-        gl[i] = *reinterpret_cast<const float4*>(p.ascale + (int64_t)b * p.ascale_bs + 4 * c);
+      // gate rows: a wave takes rows wave, wave + NW, ... (four in flight),
+      // its lanes the row's float4 -- no division.  Rows past the end fold
+      // onto the last row (the same bytes written again), so neither the
+      // loads nor the writes carry a test.
+      const int64_t bs = p.ascale_bs;
+      const int bl = p.B - 1;
+      for (int c = lane; c < c4n; c += 64) {
+        for (int b0 = wave; b0 < p.B; b0 += 4 * NW) {
+          const int b1 = min(b0 + NW, bl), b2 = min(b0 + 2 * NW, bl), b3 = min(b0 + 3 * NW, bl);
+          const float* s0 = p.ascale + 4 * c;
+          const float4 v0 = *reinterpret_cast<const float4*>(s0 + b0 * bs);
+          const float4 v1 = *reinterpret_cast<const float4*>(s0 + b1 * bs);
+          const float4 v2 = *reinterpret_cast<const float4*>(s0 + b2 * bs);
+          const float4 v3 = *reinterpret_cast<const float4*>(s0 + b3 * bs);
+          gl[b0 * c4n + c] = v0;
+          gl[b1 * c4n + c] = v1;
+          gl[b2 * c4n + c] = v2;
+          gl[b3 * c4n + c] = v3;
+        }
       }
+    }
+#pragma unroll
+    for (int q = 0; q < NI; ++q) {
+      const int i = t + q * NT;
+      if (i < nw) wl[i] = wv[q];
     }
   }
   __syncthreads();
-  const int nwv = gridDim.x * NW;
-  int blk = blockIdx.x * NW + wave;
   // ST: the shift (pixel 0's output, channels 16u + 4g .. +3 in every lane)
   float4 sh[ST ? TN : 1], ss[ST ? TN : 1], sq[ST ? TN : 1];
   if (ST) {
@@ -102,7 +177,7 @@ __global__ __launch_bounds__((CsCfg<TN, KC>::NW * 64)) void conv1x1_stream_kerne
     }
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
-      if (kc >= p.Kc) break;
+      if (!FULL && kc >= p.Kc) break;
       const int kq = kc * 16 + 4 * g;
       const float4 a = kq < p.Cin ? *reinterpret_cast<const float4*>(p.x + p.x_c0 + kq)
                                   : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -127,35 +202,29 @@ __global__ __launch_bounds__((CsCfg<TN, KC>::NW * 64)) void conv1x1_stream_kerne
     }
   }
   if (!ST && blk >= nblk) return;  // no barrier below (ST: the reduction has one)
-  const int M = (int)p.M, Cin = p.Cin, Ktot = p.Cin + (X2 ? p.Cin2 : 0);
-  const int c4n = Cin >> 2;
-  const float* xg = p.x + p.x_c0;
 
-  // one float4 of A: pixel of lane j in block bk, channels 16kc + 4g .. +3
-  auto issue = [&](int bk, int kc) -> float4 {
-    int m = bk * 16 + j;
-    m = m < M ? m : M - 1;
-    const int kq = (kc < p.Kc ? kc : p.Kc - 1) * 16 + 4 * g;
-    const float* src;
-    if (X2 && kq >= Cin) {
-      const int k2 = kq - Cin < p.Cin2 ? kq - Cin : 0;
-      src = p.x2 + m * p.x2_ps + k2;
-    } else {
-      src = xg + m * p.x_ps + (kq < Cin ? kq : 0);
-    }
-    return *reinterpret_cast<const float4*>(src);
+  // LDS operands of one stage: the TN weight fragments, and the gate float4
+  // of image gi (skip-source and padded channels read the row's first float4,
+  // which the consumer replaces by 1)
+  auto wfrag = [&](int kc, int u) -> f32x4 {
+    return wl[((FULL || kc < KC - 2 || kc < Kc ? kc : 0) * TN + u) * 64 + lane];
   };
-
-  float4 bias[TN];
+  auto gate = [&](int gi, int kc) -> float4 {
+    const int kq = kc * 16 + 4 * g;
+    const bool sel = X2 || kc >= KTAIL;
+    return gl[gi * c4n + (!sel || kq < Cin ? kq >> 2 : 0)];
+  };
+  // stage 0 of the first block; every later stage is read from the stage before
+  int gb = AS && blk < nblk ? (blk * 16) / ohw : 0;  // block-uniform (host: ohw % 16 == 0)
+  // residual row base, pixel stride and channel bound as uniform values (a
+  // null residual: stride 0 on the weights), so the loads carry no branch
+  const float* rbase = p.res ? p.res + p.res_c0 : reinterpret_cast<const float*>(p.w);
+  const int rps = p.res ? p.res_ps : 0, rcout = p.res ? p.Cout : 0;
+  f32x4 wc[TN];
+  float4 gc = make_float4(1.f, 1.f, 1.f, 1.f);
 #pragma unroll
-  for (int u = 0; u < TN; ++u) {
-    const int n0 = 16 * u + 4 * g;
-    bias[u] = p.bias && n0 < p.Cout ? *reinterpret_cast<const float4*>(p.bias + n0)
-                                    : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  float4 A[KC];
-#pragma unroll
-  for (int kc = 0; kc < KC; ++kc) A[kc] = issue(blk < nblk ? blk : 0, kc);
+  for (int u = 0; u < TN; ++u) wc[u] = wfrag(0, u);
+  if (AS) gc = gate(gb, 0);
 
   for (; blk < nblk;) {
     const int nxt = blk + nwv;
@@ -163,47 +232,97 @@ __global__ __launch_bounds__((CsCfg<TN, KC>::NW * 64)) void conv1x1_stream_kerne
     const int m = blk * 16 + j;
     // residual loads are issued unconditionally (a null residual reads the
     // first weight float4, an L2 hit) so the vmcnt of the A stages behind
-    // them stays exact
+    // them stays exact; the long-K instances, which are at the register
+    // limit, request them three quarters through the K loop (RSTAGE)
     float4 R[TN];
-    {
+    auto residual = [&]() {
       const int mr = m < M ? m : M - 1;
 #pragma unroll
       for (int u = 0; u < TN; ++u) {
         const int n0 = 16 * u + 4 * g;
-        const float* rs = p.res ? p.res + mr * p.res_ps + p.res_c0 + (n0 < p.Cout ? n0 : 0)
-                                : reinterpret_cast<const float*>(p.w);
-        R[u] = *reinterpret_cast<const float4*>(rs);
+        R[u] = *reinterpret_cast<const float4*>(rbase + mr * rps + (n0 < rcout ? n0 : 0));
       }
-    }
-    const int gb = AS ? (blk * 16) / ohw : 0;  // block-uniform (host: ohw % 16 == 0)
+    };
+    const int gbn = AS ? (bnx * 16) / ohw : 0;
     f32x4 acc[TN];
 #pragma unroll
     for (int u = 0; u < TN; ++u) acc[u] = (f32x4){bias[u].x, bias[u].y, bias[u].z, bias[u].w};
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
+      // this stage's LDS operands are in wc / gc already; each register is
+      // refilled for the next stage (the next block's stage 0 after the
+      // last) as soon as its last reader has issued
+      const int kn = kc + 1 < KC ? kc + 1 : 0;
+      const int gnx = kc + 1 < KC ? gb : gbn;
+      if (kc == RSTAGE) residual();
       float4 a = A[kc];
       const int kq = kc * 16 + 4 * g;
-      if (kc * 16 + 16 > Ktot && kq >= Ktot) a = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (AS) {  // unpredicated LDS read; skip-source channels keep scale 1
-        const bool gk = kq < Cin;
-        const float4 s = gl[gb * c4n + (gk ? kq >> 2 : 0)];
-        a.x *= gk ? s.x : 1.f; a.y *= gk ? s.y : 1.f;
-        a.z *= gk ? s.z : 1.f; a.w *= gk ? s.w : 1.f;
+      // the partial last stage and the skip source's ungated channels exist
+      // only from KTAIL on (X2: the source boundary can be anywhere)
+      if (kc >= KTAIL && kq >= Ktot) a = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (AS) {
+        if (X2 || kc >= KTAIL) {
+          const bool gk = kq < Cin;
+          a.x *= gk ? gc.x : 1.f; a.y *= gk ? gc.y : 1.f;
+          a.z *= gk ? gc.z : 1.f; a.w *= gk ? gc.w : 1.f;
+        } else {
+          a.x *= gc.x; a.y *= gc.y; a.z *= gc.z; a.w *= gc.w;
+        }
       }
-      if (kc < p.Kc) {
+      if (FULL || kc < KC - 2) {
+#pragma unroll
+        for (int u = 0; u < TN; ++u)
+          acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[u].x, a.x, acc[u], 0, 0, 0);
+        if (AS) gc = gate(gnx, kn);
+#pragma unroll
+        for (int u = 0; u < TN; ++u)
+          acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[u].y, a.y, acc[u], 0, 0, 0);
+#pragma unroll
+        for (int u = 0; u < TN; ++u)
+          acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[u].z, a.z, acc[u], 0, 0, 0);
 #pragma unroll
         for (int u = 0; u < TN; ++u) {
-          const f32x4 w = wl[(kc * TN + u) * 64 + lane];
-          acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, a.x, acc[u], 0, 0, 0);
-          acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, a.y, acc[u], 0, 0, 0);
-          acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, a.z, acc[u], 0, 0, 0);
-          acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, a.w, acc[u], 0, 0, 0);
+          acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[u].w, a.w, acc[u], 0, 0, 0);
+          wc[u] = wfrag(kn, u);
         }
+        // pin that order: x group, gate read, y and z groups, then the w
+        // group with a fragment read behind each of its MFMAs
+        __builtin_amdgcn_sched_group_barrier(0x8, TN, 0);
+        if (AS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x8, 2 * TN, 0);
+#pragma unroll
+        for (int u = 0; u < TN; ++u) {
+          __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+      } else {
+        // !FULL, last two stages: p.Kc decides (wave-uniform branch)
+        if (kc < Kc) {
+#pragma unroll
+          for (int u = 0; u < TN; ++u)
+            acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[u].x, a.x, acc[u], 0, 0, 0);
+#pragma unroll
+          for (int u = 0; u < TN; ++u)
+            acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[u].y, a.y, acc[u], 0, 0, 0);
+#pragma unroll
+          for (int u = 0; u < TN; ++u)
+            acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[u].z, a.z, acc[u], 0, 0, 0);
+#pragma unroll
+          for (int u = 0; u < TN; ++u)
+            acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[u].w, a.w, acc[u], 0, 0, 0);
+        }
+        if (AS) gc = gate(gnx, kn);
+#pragma unroll
+        for (int u = 0; u < TN; ++u) wc[u] = wfrag(kn, u);
       }
       // refill after the MFMAs have read the stage: the load can take the
       // stage's own registers (no loop-carried copy, which would wait vmcnt(0))
       A[kc] = issue(bnx, kc);
+      // a stage's reads stay in that stage: without this the scheduler hoists
+      // every stage's LDS reads to the top of the block and spills them
+      __builtin_amdgcn_sched_barrier(0);
     }
+    gb = gbn;
     // acc[u][r] = Y[pixel m][16u + 4g + r]
     if (m < M) {
 #pragma unroll
@@ -301,6 +420,32 @@ static int stream_grid(Kern kern, int threads, size_t lds, int64_t nwg) {
   X(1, 1) X(2, 1) X(3, 1) X(4, 1) X(5, 1) X(1, 2) X(2, 2) X(3, 2) X(4, 2) X(5, 2) \
   X(1, 3) X(2, 3) X(3, 3) X(4, 3) X(5, 3) X(1, 4) X(2, 4) X(3, 4) X(4, 4) X(5, 4)
 
+// The KC that stream_kc rounds a smaller Kc up to: only these also have the
+// !FULL form; every other KC is reached by Kc == KC alone.
+static constexpr bool stream_kc_rounds(int kc) {
+  return kc == 8 || kc == 10 || kc == 12 || kc == 16 || kc == 18;
+}
+
+template <int TN, int KC, int X2, bool AS, bool FULL>
+static int stream_launch_form(const ConvArgs& a, hipStream_t st, size_t lds, int64_t nblk,
+                              int64_t ohw) {
+  auto kern = conv1x1_stream_kernel<TN, KC, X2, AS, false, FULL>;
+  constexpr int nw = CsCfg<TN, KC>::NW;
+  const int grid = stream_grid(kern, nw * 64, lds, cdiv(nblk, nw));
+  if (grid < 1) return -1;
+  kern<<<grid, nw * 64, lds, st>>>(a, (int)nblk, (int)ohw, nullptr, nullptr);
+  return check_launch("conv1x1_stream", 100 * KC + TN);
+}
+
+template <int TN, int KC, int X2, bool AS>
+static int stream_launch(const ConvArgs& a, hipStream_t st, size_t lds, int64_t nblk,
+                         int64_t ohw) {
+  if (a.Kc == KC) return stream_launch_form<TN, KC, X2, AS, true>(a, st, lds, nblk, ohw);
+  if constexpr (stream_kc_rounds(KC))
+    return stream_launch_form<TN, KC, X2, AS, false>(a, st, lds, nblk, ohw);
+  return -1;
+}
+
 // Whether this kernel serves a layer of the fast-1x1 layouts (contiguous NHWC
 // rows, v4 epilogue, x2 at the same resolution); stats: its statistics form
 // (no gate, no second source, no residual).  The route (conv.hip) and the
@@ -327,6 +472,8 @@ bool conv1x1_stream_serves(const ConvArgs& a, bool stats) {
   // the instance's wave count (CsCfg, from the rounded KC) must be the one the
   // LDS bound above assumed (from Kc)
   if ((a.Kc * TN > 24) != (KC * TN > 24)) return false;
+  // the !FULL form tests p.Kc on its last two stages only
+  if (KC - a.Kc > 2 || (KC != a.Kc && !stream_kc_rounds(KC))) return false;
 #define CS_HAS(TN_, KC_) \
   if (TN == TN_ && KC == KC_) return true;
   CS_INSTANCES(CS_HAS)
@@ -348,14 +495,7 @@ int conv1x1_stream_dispatch(const ConvArgs& a, hipStream_t st, StreamStats* ss) 
   const int x2 = a.x2 ? 1 : 0;
   const bool as = a.ascale != nullptr;
 #define CS_LAUNCH(TN_, KC_, X2_, AS_)                                                       \
-  do {                                                                                      \
-    auto kern = conv1x1_stream_kernel<TN_, KC_, X2_, AS_>;                                  \
-    constexpr int nw_ = CsCfg<TN_, KC_>::NW;                                                \
-    const int grid = stream_grid(kern, nw_ * 64, lds, cdiv(nblk, nw_));                     \
-    if (grid < 1) return -1;                                                                \
-    kern<<<grid, nw_ * 64, lds, st>>>(a, (int)nblk, (int)ohw, nullptr, nullptr);            \
-    return check_launch("conv1x1_stream", 100 * KC_ + TN_);                                 \
-  } while (0)
+  return stream_launch<TN_, KC_, X2_, AS_>(a, st, lds, nblk, ohw)
 #define CS_LAUNCH_ST(TN_, KC_)                                                              \
   do {                                                                                      \
     auto kern = conv1x1_stream_kernel<TN_, KC_, 0, false, true>;                            \
