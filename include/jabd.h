@@ -447,6 +447,84 @@ int jabd_batch_collect_f32(const float* rows, const int64_t* n_keep, int64_t n,
                            int64_t cap, int64_t* offsets, jabd_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * jabd_align_faces_u8: aligned face crops from the five landmarks of detect
+ * rows, for every face of a chunk of mixed-size images in one launch.  The
+ * semantics are the project's own (cv2's pixel-centre convention, not its
+ * fixed-point warpAffine) and are stated so that tests/_align_ref.py restates
+ * them bit for bit in numpy.
+ *   pool, pool_bytes, desc   the byte pool and slot table [n_images, 3] of
+ *            jabd_letterbox_batch_u8 (RGB HWC uint8 images back to back).
+ *   rows     device float32 [cap, 15] in image pixels and offsets device int64
+ *            [n_images + 1], as jabd_batch_collect_f32 leaves them.  The face
+ *            count min(offsets[n_images], cap) is read on the device; face r
+ *            belongs to the image i with offsets[i] <= r < offsets[i + 1],
+ *            found on the device by a binary search of offsets.
+ *   template10  host float[10]: five (x, y) destination points of the size x
+ *            size crop, in the order of a row's columns 5..14 (left eye, right
+ *            eye, nose, left and right mouth corner).
+ *   fit      a least-squares similarity (rotation, uniform scale,
+ *            translation, no reflection) from the row's landmarks p_i to the
+ *            template q_i, in double, no contraction, every sum in index order
+ *            from 0.0: both sets are centred on their means (sum / 5.0);
+ *            S = sum(px*px + py*py), A = sum(px*qx + py*qy),
+ *            B = sum(px*qy - py*qx); a = A / S, b = B / S;
+ *            tx = mqx - (a*mpx - b*mpy), ty = mqy - (b*mpx + a*mpy);
+ *            M = [[a, -b, tx], [b, a, ty]] (Umeyama's estimate with its
+ *            reflection guard, in closed form: no SVD, no transcendental).
+ *   invalid  a face with a non-finite landmark, S == 0, a == b == 0 (or
+ *            a*a + b*b not a positive finite double), or whose image slot is
+ *            empty (ih <= 0 or iw <= 0 or either beyond INT32_MAX, or its bytes
+ *            [offset, offset + 3 * ih * iw) not inside [0, pool_bytes)): its
+ *            crop is 0 everywhere (float output: (0 - mean) / std), its matrix
+ *            six zeros, and nothing is read from pool for it.
+ *   sampling integer coordinates are pixel centres.  det = a*a + b*b, ia =
+ *            a / det, ib = b / det.  Crop pixel (x, y) is the mean of s x s
+ *            sub-samples, rows outer, columns inner; sub-sample j of an axis
+ *            lies at u = (x + (j + 0.5) / s) - 0.5.  s is the smallest of 1, 2,
+ *            3, 4 with s*s*det >= 1 (s * scale >= 1 without the root), 4 if
+ *            none; always 1 with antialias == 0.  Per sub-sample, in double:
+ *            du = u - tx, dv = v - ty, sx = ia*du + ib*dv, sy = ia*dv - ib*du,
+ *            fx = floor(sx), fy = floor(sy).  Unless -1 <= fx <= iw - 1 and
+ *            -1 <= fy <= ih - 1 the sub-sample is 0.  Otherwise wx = (float)(sx
+ *            - fx), wy likewise, and per channel in float32, a tap outside the
+ *            image being 0 (each tap tested on its own):
+ *              top = p00 * (1 - wx) + p01 * wx,  bot = p10 * (1 - wx) + p11 * wx,
+ *              t   = top * (1 - wy) + bot * wy
+ *            (pYX: Y the row fy / fy + 1, X the column fx / fx + 1).  The
+ *            sub-samples are added in float32 from 0 in their order and the
+ *            sum is divided by (float)(s*s).
+ *   out_kind JABD_ALIGN_U8_HWC: crops uint8 [cap, size, size, 3] RGB, rintf of
+ *            that value (round half to even); bgr, mean3, std3 are not used
+ *            (they may be NULL).  JABD_ALIGN_F32_NCHW: crops float32 [cap, 3,
+ *            size, size]; plane k holds (t - mean3[k]) / std3[k] of the
+ *            unrounded value of source channel k, or 2 - k when bgr != 0.
+ *            mean3, std3: host float[3].
+ *   matrices device float32 [cap, 6] = (a, -b, tx, b, a, ty), each rounded once
+ *            from the double fit; may be NULL.
+ * One launch (the fit is made again by every workgroup of a face; there is no
+ * launch in front), sized by cap: workgroups of faces beyond the count exit,
+ * and crops and matrices beyond it are not written.  One thread makes four
+ * consecutive pixels of a crop row and stores 12 bytes (uint8) or three 16-byte
+ * plane stores (float): launch tag 4; a size that is no multiple of 4, or crops
+ * not 4-byte (float: 16-byte) aligned, takes the one-pixel form, tag 1.  No
+ * workspace, no host synchronisation, no memset, no atomics: the call can be
+ * captured in a HIP graph and two runs give identical bytes.  cap == 0 or
+ * n_images == 0 launches nothing.  JABD_EINVAL: size < 1 or size > 1024, a
+ * zero or non-finite std3 entry, a non-finite mean3 or template entry, an
+ * unknown out_kind, cap * ceil(size * size / 1024) (one-pixel form: / 256)
+ * beyond INT32_MAX.
+ * ------------------------------------------------------------------------ */
+enum {
+  JABD_ALIGN_U8_HWC = 0,
+  JABD_ALIGN_F32_NCHW = 1,
+};
+int jabd_align_faces_u8(const uint8_t* pool, int64_t pool_bytes, const int64_t* desc,
+                        int64_t n_images, const float* rows, const int64_t* offsets,
+                        int64_t cap, const float* template10, int size, int antialias,
+                        int out_kind, const float* mean3, const float* std3, int bgr,
+                        void* crops, float* matrices, jabd_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * A7/A8 anchor matching + encoding — nets/retinaface_training.py:93-162
  * (match/encode/encode_landm) for a whole batch in one pass.
  *   targets  [T, 15] device fp32: the B per-image target tensors concatenated

@@ -148,6 +148,8 @@ SIGNATURES = {
     "jabd_letterbox_batch_u8": [c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_f32, c_vp, c_vp],
     "jabd_batch_collect_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_int, c_int, c_i64, c_vp, c_i64,
                                c_vp, c_vp],
+    "jabd_align_faces_u8": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_int, c_int,
+                            c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp],
     "jabd_match_workspace_size": [c_i64, c_i64, c_sizep],
     "jabd_match_encode_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_f32, c_f32, c_f32,
                               c_vp, c_vp, c_vp, c_vp, c_size, c_vp],

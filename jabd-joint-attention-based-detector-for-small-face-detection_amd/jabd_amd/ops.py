@@ -536,6 +536,97 @@ def batch_collect(rows, n_keep, desc, input_shape, max_det=0, out=None, offsets=
     return out, offsets
 
 
+# the widely used ArcFace five-point template of a 112 x 112 crop: left eye,
+# right eye, nose, left and right mouth corner (a row's columns 5..14)
+ARCFACE_112 = ((38.2946, 51.6963), (73.5318, 51.5014), (56.0252, 71.7366),
+               (41.5493, 92.3655), (70.7299, 92.2041))
+
+
+def align_template(size=112):
+    """Host only: the default template of ops.align_faces for a size x size
+    crop, float32 [5, 2]: ARCFACE_112 * (size / 112), formed in double."""
+    return (np.array(ARCFACE_112, np.float64) * (float(size) / 112.0)).astype(np.float32)
+
+
+def _align_args(name, size, template, out, mean, std):
+    """Checked host arguments of align_faces: (size, template float32 [10],
+    out_kind, mean float32 [3], std float32 [3])."""
+    if int(size) != size or not 1 <= int(size) <= 1024:
+        raise ValueError(f"{name}: size must be an int in [1, 1024], got {size!r}")
+    size = int(size)
+    if template is None:
+        q = align_template(size)
+    else:
+        q = np.asarray(template, np.float32)
+        if q.shape != (5, 2) or not np.isfinite(q).all():
+            raise ValueError(f"{name}: template must be five finite (x, y) points")
+    if out not in ("u8", "f32"):
+        raise ValueError(f"{name}: out must be 'u8' or 'f32', got {out!r}")
+    m = np.ascontiguousarray(np.broadcast_to(np.asarray(mean, np.float32), (3,)))
+    s = np.ascontiguousarray(np.broadcast_to(np.asarray(std, np.float32), (3,)))
+    if not (np.isfinite(m).all() and np.isfinite(s).all() and (s != 0).all()):
+        raise ValueError(f"{name}: mean must be finite and std finite and non-zero")
+    return size, np.ascontiguousarray(q.reshape(10)), 0 if out == "u8" else 1, m, s
+
+
+def align_faces(pool, desc, rows, offsets, size=112, template=None, antialias=True, out="u8",
+                mean=127.5, std=127.5, bgr=False, crops=None, matrices=None, pool_bytes=None):
+    """Aligned face crops from detect rows, on the device
+    (jabd_align_faces_u8).  pool device uint8 1-D and desc device int64 [n, 3]
+    as ops.pack_images lays them out; rows device float32 [cap, 15] in image
+    pixels and offsets device int64 [n + 1] as ops.batch_collect returns them:
+    the first min(offsets[n], cap) rows are faces, face r belonging to image i
+    with offsets[i] <= r < offsets[i + 1].  Each face's landmarks are fitted
+    to `template` (float32 [5, 2] crop coordinates; default align_template(size))
+    by a least-squares similarity, and the image is warped into a size x size
+    crop, bilinear, with up to 4 x 4 sub-samples per pixel where the face is
+    scaled down (antialias=False: always one).  out "u8": crops uint8 [cap,
+    size, size, 3] RGB; "f32": float32 [cap, 3, size, size], plane k = (value -
+    mean[k]) / std[k] of channel k, or of channel 2 - k with bgr (mean, std: a
+    number or three).  An invalid face (a non-finite landmark, coinciding
+    landmarks, an empty slot) gives a crop of zeros ("f32": of (0 - mean) / std)
+    and a zero matrix.  Returns (crops, matrices): matrices float32 [cap, 6] =
+    the 2 x 3 forward matrix (a, -b, tx, b, a, ty) per face; matrices=False
+    skips them (None is returned in their place).  crops / matrices may be
+    given (contiguous device tensors of those shapes); entries of faces beyond
+    the count are not written.  No workspace and no host synchronisation.
+    pool_bytes as in letterbox_batch."""
+    pool = _dev("align_faces.pool", pool, torch.uint8)
+    if pool.dim() != 1:
+        raise ValueError(f"align_faces: pool must be 1-D, got {tuple(pool.shape)}")
+    desc = _batch_desc("align_faces", desc)
+    rows = _dev("align_faces.rows", rows)
+    offsets = _dev("align_faces.offsets", offsets, torch.int64)
+    if rows.dim() != 2 or rows.shape[1] != 15:
+        raise ValueError(f"align_faces: rows must be [cap, 15], got {tuple(rows.shape)}")
+    n, cap = desc.shape[0], rows.shape[0]
+    if offsets.dim() != 1 or offsets.numel() < n + 1:
+        raise ValueError(f"align_faces: offsets needs {n + 1} entries")
+    size, q, kind, m, s = _align_args("align_faces", size, template, out, mean, std)
+    nbytes = pool.numel() if pool_bytes is None else int(pool_bytes)
+    if not 0 <= nbytes <= pool.numel():
+        raise ValueError(f"align_faces: pool_bytes {nbytes} outside [0, {pool.numel()}]")
+    shape = (cap, size, size, 3) if kind == 0 else (cap, 3, size, size)
+    dtype = torch.uint8 if kind == 0 else torch.float32
+    if crops is None:
+        crops = torch.empty(shape, dtype=dtype, device=rows.device)
+    if matrices is None:
+        matrices = torch.empty((cap, 6), dtype=torch.float32, device=rows.device)
+    elif matrices is False:
+        matrices = None
+    for name, t, dt, shp in (("crops", crops, dtype, shape),
+                             ("matrices", matrices, torch.float32, (cap, 6))):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt
+                                  and t.is_contiguous() and tuple(t.shape) == shp):
+            raise ValueError(f"align_faces: {name} must be a contiguous device {dt} tensor of "
+                             f"shape {shp}")
+    call("jabd_align_faces_u8", _p(pool), nbytes, _p(desc), n, _p(rows), _p(offsets), cap,
+         ctypes.c_void_p(q.ctypes.data), size, 1 if antialias else 0, kind,
+         ctypes.c_void_p(m.ctypes.data), ctypes.c_void_p(s.ctypes.data), 1 if bgr else 0,
+         _p(crops), _p(matrices), _stream())
+    return crops, matrices
+
+
 def detect(loc, conf, landm, priors, variances, conf_threshold=0.5, nms_threshold=0.3,
            nms_kind="greedynms", beta1=1.0, top_k=0, sigma=0.5, soft_offset=0.0):
     """predict.py:162-181 on device for a batch: decode + filter + NMS.

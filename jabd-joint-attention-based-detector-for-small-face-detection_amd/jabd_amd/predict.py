@@ -198,13 +198,31 @@ def detect_images(net, images, input_shape, cfg, batch=8, max_det=750, confidenc
     result buffers): chunk c + 1 is packed and enqueued before chunk c's event
     is waited on, and that wait is the chunk's only host synchronisation
     (max_det <= 0: one more, for the rows)."""
+    return _detect_chunks("detect_images", None, net, images, input_shape, cfg, batch, max_det,
+                          confidence, nms_iou, device, nms_kind, beta1, top_k, sigma, soft_offset)
+
+
+def _detect_chunks(name, extra, net, images, input_shape, cfg, batch, max_det, confidence,
+                   nms_iou, device, nms_kind, beta1, top_k, sigma, soft_offset):
+    """The chunk pipeline of detect_images (its docstring).  extra: None, or
+    the private hook of extract_faces, an object with
+      enqueue(pool, table, out, offsets) -> device uint8 1-D tensor
+        called behind the chunk's ops.batch_collect with the chunk's device
+        byte pool and slot table and the collected rows [cap, 15] and offsets
+        [batch + 1]; what it returns is downloaded into a pinned buffer of its
+        own by one more non-blocking copy in front of the chunk's event, so the
+        chunk still has one host synchronisation;
+      finish(host, rows, offs, n) -> list of n per-image results
+        called behind that wait with the downloaded bytes (numpy uint8), the
+        chunk's host rows and offsets and its number of images; its results
+        replace the per-image rows."""
     import itertools
     batch = int(batch)
     if batch < 1:
-        raise ValueError(f"detect_images: batch must be at least 1, got {batch}")
+        raise ValueError(f"{name}: batch must be at least 1, got {batch}")
     H, W = _pair("input_shape", input_shape)
     if H < 1 or W < 1:
-        raise ValueError(f"detect_images: bad input shape {input_shape!r}")
+        raise ValueError(f"{name}: bad input shape {input_shape!r}")
     if ops.is_soft_kind(nms_kind):
         ops._soft_args(sigma, soft_offset)
     else:
@@ -212,7 +230,7 @@ def detect_images(net, images, input_shape, cfg, batch=8, max_det=750, confidenc
     max_det = max(int(max_det), 0)
     it = iter(images)
     head = batch * 24                      # the slot table leads the staging buffer
-    stage, result = {}, {}
+    stage, result, side = {}, {}, {}
     state = {}
 
     def setup():
@@ -222,7 +240,7 @@ def detect_images(net, images, input_shape, cfg, batch=8, max_det=750, confidenc
                      graph=_use_graph(net, (H, W, str(device)), True))
 
     def enqueue(chunk, first, slot):
-        arrs, desc, total = ops._pack_arrays("detect_images", chunk, (W, H), first)
+        arrs, desc, total = ops._pack_arrays(name, chunk, (W, H), first)
         buf = _pinned(stage, slot, head + total)
         host = buf.numpy()
         table = host[:head].view(np.int64).reshape(batch, 3)
@@ -255,12 +273,17 @@ def detect_images(net, images, input_shape, cfg, batch=8, max_det=750, confidenc
         back = res if max_det else res[:tail]
         hres = _pinned(result, slot, back.numel())[:back.numel()]
         hres.copy_(back, non_blocking=True)
+        hside = None
+        if extra is not None:
+            more = extra.enqueue(dev[head:], table, out, offsets)
+            hside = _pinned(side, slot, more.numel())[:more.numel()]
+            hside.copy_(more, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
-        return len(arrs), hres, out, done
+        return len(arrs), hres, out, done, hside
 
     def finish(job):
-        n, hres, out, done = job
+        n, hres, out, done, hside = job
         done.synchronize()
         host = hres.numpy()
         tail = (batch + 1) * 8
@@ -269,6 +292,8 @@ def detect_images(net, images, input_shape, cfg, batch=8, max_det=750, confidenc
             rows = host[tail:].view(np.float32).reshape(-1, 15)
         else:                              # no cap: the rows that exist, one more wait
             rows = out[:int(offs[n])].cpu().numpy()
+        if extra is not None:
+            return extra.finish(hside.numpy(), rows, offs, n)
         return [rows[offs[i]:offs[i + 1]].copy() for i in range(n)]
 
     results, pending, first = [], None, 0
@@ -285,6 +310,95 @@ def detect_images(net, images, input_shape, cfg, batch=8, max_det=750, confidenc
         if pending is not None:
             results += finish(pending)
     return results
+
+
+def _crop_layout(size, kind):
+    """(shape, numpy dtype, bytes) of one crop."""
+    if kind == 0:
+        return (size, size, 3), np.uint8, size * size * 3
+    return (3, size, size), np.float32, size * size * 12
+
+
+def align_faces(image, dets, size=112, template=None, antialias=True, out="u8", mean=127.5,
+                std=127.5, bgr=False, device="cuda"):
+    """Aligned crops of one image's detections (ops.align_faces).  image: RGB
+    HWC uint8 array; dets: the [K, 15] rows any of the detect functions
+    returned for it (image pixels), or [].  Returns numpy (crops, matrices):
+    crops uint8 [K, size, size, 3], or float32 [K, 3, size, size] with
+    out="f32"; matrices float32 [K, 6].  [] or K == 0 gives arrays of length 0
+    without device work.  The other arguments are ops.align_faces'."""
+    size, _, kind, _, _ = ops._align_args("align_faces", size, template, out, mean, std)
+    shape, dtype, _ = _crop_layout(size, kind)
+    arr = ops._image_u8("align_faces", 0, image)
+    rows = np.asarray(dets, np.float32)
+    if rows.size == 0:
+        return np.zeros((0,) + shape, dtype), np.zeros((0, 6), np.float32)
+    if rows.ndim != 2 or rows.shape[1] != 15:
+        raise ValueError(f"align_faces: dets must be [K, 15], got {rows.shape}")
+    K = rows.shape[0]
+    pool = torch.from_numpy(np.ascontiguousarray(arr).reshape(-1)).to(device)
+    desc = torch.tensor([[0, arr.shape[0], arr.shape[1]]], dtype=torch.int64, device=device)
+    offsets = torch.tensor([0, K], dtype=torch.int64, device=device)
+    crops, matrices = ops.align_faces(pool, desc, torch.from_numpy(np.ascontiguousarray(rows))
+                                      .to(device), offsets, size=size, template=template,
+                                      antialias=antialias, out=out, mean=mean, std=std, bgr=bgr)
+    return crops.cpu().numpy(), matrices.cpu().numpy()
+
+
+class _AlignHook:
+    """extract_faces' side of _detect_chunks: ops.align_faces on the chunk's
+    own device pool and collected rows, crops and matrices packed into one
+    device buffer (the matrices lead, so both stay aligned)."""
+
+    def __init__(self, size, template, antialias, out, mean, std, bgr):
+        self.size, _, self.kind, _, _ = ops._align_args("extract_faces", size, template, out,
+                                                        mean, std)
+        self.kw = dict(size=self.size, template=template, antialias=antialias, out=out,
+                       mean=mean, std=std, bgr=bgr)
+
+    def enqueue(self, pool, table, out, offsets):
+        cap = self.cap = out.shape[0]             # the same for every chunk of a call
+        shape, _, nbytes = _crop_layout(self.size, self.kind)
+        lead = -(-cap * 24 // 16) * 16            # the crops start on a 16-byte boundary
+        buf = torch.empty(lead + cap * nbytes, dtype=torch.uint8, device=out.device)
+        matrices = buf[:cap * 24].view(torch.float32).view(cap, 6)
+        crops = buf[lead:]
+        crops = (crops if self.kind == 0 else crops.view(torch.float32)).view((cap,) + shape)
+        ops.align_faces(pool, table, out, offsets, crops=crops, matrices=matrices, **self.kw)
+        return buf
+
+    def finish(self, host, rows, offs, n):
+        cap = self.cap
+        shape, dtype, _ = _crop_layout(self.size, self.kind)
+        matrices = host[:cap * 24].view(np.float32).reshape(cap, 6)
+        crops = host[-(-cap * 24 // 16) * 16:].view(dtype).reshape((cap,) + shape)
+        return [(rows[offs[i]:offs[i + 1]].copy(), crops[offs[i]:offs[i + 1]].copy(),
+                 matrices[offs[i]:offs[i + 1]].copy()) for i in range(n)]
+
+
+def extract_faces(net, images, input_shape, cfg, size=112, batch=8, max_det=750, confidence=0.5,
+                  nms_iou=0.3, device="cuda", nms_kind="greedynms", beta1=1.0, top_k=0,
+                  sigma=0.5, soft_offset=0.0, template=None, antialias=True, out="u8",
+                  mean=127.5, std=127.5, bgr=False):
+    """detect_images plus the aligned crop of every detection, made on the
+    device from the chunk's own byte pool and collected rows before the pool
+    is released (ops.align_faces; size, template, antialias, out, mean, std,
+    bgr are its arguments, the others detect_images').  Returns one (rows,
+    crops, matrices) per image, in order: rows exactly detect_images' [K_i, 15],
+    crops uint8 [K_i, size, size, 3] (out="f32": float32 [K_i, 3, size, size]),
+    matrices float32 [K_i, 6].  The chunk pipeline is detect_images' own: the
+    crops and matrices of a chunk come back in a second pinned buffer by a
+    second non-blocking copy in front of the chunk's one event, so the chunk
+    still synchronises once.  That buffer holds batch * max_det crops whatever
+    the number of faces, size * size * 3 bytes each (out="f32": four times
+    that), twice on the host and up to twice on the device; max_det <= 0 would
+    size it by the number of anchors and raises ValueError."""
+    if int(max_det) <= 0:
+        raise ValueError(f"extract_faces: max_det must be positive, got {max_det!r} (the crop "
+                         "buffer holds batch * max_det crops)")
+    hook = _AlignHook(size, template, antialias, out, mean, std, bgr)
+    return _detect_chunks("extract_faces", hook, net, images, input_shape, cfg, batch, max_det,
+                          confidence, nms_iou, device, nms_kind, beta1, top_k, sigma, soft_offset)
 
 
 def _tta_passes(net, img, cfg, scales, flip, confidence, nms_iou, device, nms_kind, beta1, top_k):
