@@ -2728,6 +2728,7 @@ static int dw_wgrad(const float* x, const float* dy, int32_t B, int32_t H, int32
   // 3x3: the row-walking kernel when (image, band) pairs leave room for row
   // chunks within the 1024 partial blocks (JABD_DW_WGRAD_ROWS=0: strip kernel)
   static const bool rows_on = env_digit("JABD_DW_WGRAD_ROWS") != 0;
+  bool rows = false;  // launch witness: the row walker logs its own name
 #define WR_CASE(S_, PW_)                                                                        \
   if (rows_on && k == 3 && stride == S_) {                                                      \
     const int nstrip = (int)cdiv(OW, PW_);                                                      \
@@ -2737,6 +2738,7 @@ static int dw_wgrad(const float* x, const float* dy, int32_t B, int32_t H, int32
       const int R = (int)cdiv(OH, want);                                                        \
       const int nch = (int)cdiv(OH, R);                                                         \
       nblk = (int64_t)B * nbands * nch;                                                         \
+      rows = true;                                                                              \
       dim3 g((unsigned)nblk, (unsigned)cdiv(C4, lanes));                                        \
       if (it)                                                                                   \
         dw_wgrad_rows_kernel<S_, PW_, true><<<g, 256, 0, st>>>(                                 \
@@ -2767,7 +2769,7 @@ static int dw_wgrad(const float* x, const float* dy, int32_t B, int32_t H, int32
   }
   WG_CASE(3, 1, 8) WG_CASE(3, 2, 4) WG_CASE(5, 1, 4) WG_CASE(5, 2, 4)
 #undef WG_CASE
-  if (int e = check_launch("dw_wgrad")) return e;
+  if (int e = check_launch(rows ? "dw_wgrad_rows" : "dw_wgrad")) return e;
   const int64_t tot = (int64_t)k * k * C;
   const int rl = tot >= 64 * 512 ? 64 : 16;
   wgrad_reduce2_kernel<<<(unsigned)cdiv(tot, rl), 256, 0, st>>>(part, nblk, k * k, C, 1, k * k, rl,
